@@ -56,6 +56,59 @@ HBM_PEAK_GBS = 8000.0      # MI355X HBM3E spec peak (MI355X_MICROARCH.md)
 DIRECT_NAMES = {0: "none", 1: "spatial", 2: "temporal", 3: "auto"}
 ME_NAMES = {0: "dia", 1: "hex", 2: "umh", 3: "esa"}
 CAPTURE = 1 << 20          # bytes of chain 0's payload copied out per step for the parity check
+DUMP_BYTES = 60 << 20      # --dump-outputs: at most this many bytes of .npy data in all (under 64 MB)
+DUMP_SEED = 20090216       # --dump-outputs: the fixed order in which chains enter the payload / state sample
+
+
+def dump_order(n):
+    """Chain indices 0..n-1 in a fixed, seeded order whose relative order does not depend on n (a run that fits fewer chains samples the
+    same chains first)."""
+    keys = np.random.default_rng(DUMP_SEED).random(max(n, 1 << 16))[:n]
+    return np.argsort(keys, kind="stable")
+
+
+def save_dump(path, arrays):
+    """Write {name: array} as path/<name>.npy (float32 / float64 only), within DUMP_BYTES."""
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_BYTES, "bench.py --dump-outputs: %d bytes" % total
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(path, name + ".npy"), a)
+    print("bench.py: --dump-outputs wrote %s (%d bytes)" % (", ".join(sorted(arrays)), total), file=sys.stderr)
+
+
+def read_payload(hip, rb, cap, b):
+    """Chain b's slice payload (the bytes a caller downloads) from buffer set rb, after the device is synchronised."""
+    n = np.zeros(1, np.int32)
+    assert hip.x264hip_memcpy_d2h(n.ctypes.data_as(C.c_void_p), C.c_void_p(rb["payload_len"].ptr + 4 * b), C.c_size_t(4)) == 0
+    assert 0 <= n[0] <= cap - sl.PAYLOAD_LEAD, "chain %d: payload length %d outside its %d-byte buffer" % (b, n[0], cap)
+    out = np.zeros(int(n[0]), np.uint8)
+    if out.size:
+        assert hip.x264hip_memcpy_d2h(out.ctypes.data_as(C.c_void_p), C.c_void_p(rb["payload"].ptr + cap * b + sl.PAYLOAD_LEAD), C.c_size_t(out.size)) == 0
+    return out
+
+
+def dump_payloads(path, rows, pays):
+    """What a caller of the timed path receives from its last step, for every chain of this process in job order: rows[i] = that chain's
+    frame decision, pays[i] = its slice payload (uint8).  Written:
+      frame_decisions  float64 [chains, columns of rows] + the payload's length in bytes as the last column
+      payload_digest   float64 [chains]: the first 48 bits of each payload's md5, as an integer (exact in float64)
+      payload_sample   float32 [bytes]: the payloads of the chains of dump_order, concatenated, as many whole ones as the budget holds
+      payload_sample_chains  float64 [chains sampled]: which chains, in the order of payload_sample"""
+    import hashlib
+    dec = np.array([list(r) + [len(p)] for r, p in zip(rows, pays)], np.float64)
+    dig = np.array([int(hashlib.md5(p.tobytes()).hexdigest()[:12], 16) for p in pays], np.float64)
+    room = (DUMP_BYTES - dec.nbytes - dig.nbytes - 8 * len(pays)) // 4
+    pick = []
+    for i in dump_order(len(pays)):
+        if len(pays[i]) > room:
+            break
+        room -= len(pays[i])
+        pick.append(int(i))
+    sample = np.concatenate([pays[i] for i in pick]).astype(np.float32) if pick else np.zeros(0, np.float32)
+    save_dump(path, {"frame_decisions": dec, "payload_digest": dig, "payload_sample": sample,
+                     "payload_sample_chains": np.array(pick, np.float64)})
 
 
 def analysis_options(args):
@@ -358,6 +411,14 @@ def run_stream(args, hip, dist, json_fd, rank, world, B, g_first, g_step, cpu, r
                                  "(%d bytes)" % (k, frame, n, len(want)))
             checked += 1
         hip.x264hip_host_free(C.c_void_p(pin))
+    if args.dump_outputs and rank == 0:                  # the last timed step of every chain: what x264_encoder_encode returned for it
+        rows, pays = [], []
+        for e in encs:
+            rb = getattr(e, "last_bufs", None) or e.rd_bufs
+            for b, cd in enumerate(e.coded_now):
+                rows.append((cd.frame, cd.type, cd.slice_type, cd.qp, cd.f_qpm, cd.poc))
+                pays.append(read_payload(hip, rb, e.payload_cap, b))
+        dump_payloads(args.dump_outputs, rows, pays)
 
     # the dominant kernels, timed live with HIP events on their launch stream: per step and group the chain-table launches together
     evs = [ev for e in encs for ev in e.sweep_events]
@@ -522,6 +583,13 @@ def run_stream_async(args, hip, dist, json_fd, rank, world, B, g_first, g_step, 
                                  "(%d bytes)" % (k, frame, n, len(want)))
             checked += 1
         hip.x264hip_host_free(C.c_void_p(pin))
+    if args.dump_outputs and rank == 0:                  # every chain's last coded frame (each chain's own last launch)
+        rows, pays = [], []
+        for b, per in enumerate(enc.coded_all):
+            cd = per[-1]
+            rows.append((cd.frame, cd.type, cd.slice_type, cd.qp, cd.f_qpm, cd.poc))
+            pays.append(read_payload(hip, enc.payload_bufs(len(per) - 1, b), enc.payload_cap, b))
+        dump_payloads(args.dump_outputs, rows, pays)
     evs = enc.sweep_events
     ms_all = [hip.x264hip_event_elapsed_ms(C.c_void_p(a), C.c_void_p(b)) for a, b, _, _, _ in evs]
     n_ip = [n for _, _, n, _, _ in evs]
@@ -661,7 +729,12 @@ def main():
     ap.add_argument("--scenecut", type=int, default=40, help="param.i_scenecut_threshold")
     ap.add_argument("--pre-scenecut", dest="pre_scenecut", type=int, default=0, help="stream mode: 1: the scene cut decided in the lookahead (what the reference forces with --threads > 1); "
                     "0 (the reference's default): x264_encoder_encode's look at every coded P frame, a given-up attempt coded again inside the step")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="after the timed steps, write what the last step gave its caller as DIR/<name>.npy (float32 / float64, "
+                    "at most 64 MB; rank 0 only): stream and lock-step modes with a payload -- frame_decisions, payload_digest, payload_sample, payload_sample_chains "
+                    "(dump_payloads); the wavefront variant without one -- the decision arrays of a seeded sample of chains (state_<name>, state_chains)")
     args = ap.parse_args()
+    if args.steps < 0 or args.warmup < -1:
+        raise SystemExit("bench.py: --steps and --warmup must not be negative")
     args.cif = args.preset == "cif"
     if args.cif:
         args.wavefront, args.stream, args.subme_zero = 1, 0, True
@@ -762,14 +835,16 @@ def main():
     cap_n = min(CAPTURE, (enc.payload_cap if args.cif else args.payload_cap) - sl.PAYLOAD_LEAD)
     pin = hip.x264hip_host_alloc(C.c_size_t(n_coded * (cap_n + 64))) if check else None
 
+    last = []                                        # display index, slice type, QP and state of the latest step
+
     def one_step(k):
         disp, stype = order[k]
         src = srcs[k % len(srcs)]
         ctx.synth(src, clip_time(disp, g_first, args.keyint, g_total), g_step * args.keyint)
         if stype is None:
-            enc.encode_frame(src)
+            last[:] = (disp,) + enc.encode_frame(src)
         else:
-            enc.encode_frame(src, stype=stype, disp=disp)
+            last[:] = (disp,) + enc.encode_frame(src, stype=stype, disp=disp)
         if check and k < len(ref_pays):
             enc.payload_async(0, pin + k * (cap_n + 64), pin + k * (cap_n + 64) + 64, cap_n)
         enc.finish_frame()
@@ -832,6 +907,18 @@ def main():
             stream_md5 = ("chain 0's whole Annex B stream of its first 30 frames (the cif30 clip: version SEI, SPS, PPS, slice headers, CAVLC payloads) has the md5 of the "
                           "reference command line's output for BASELINE config 1, 02b208eecef842e084cbb9c83bc1a757")
         hip.x264hip_host_free(C.c_void_p(pin))
+    if args.dump_outputs and rank == 0:                  # the last timed step: every chain coded the same frame of its own GOP
+        disp, stype, qp, state = last
+        if (enc.raster and enc.rd_opt["write"]) or enc.cavlc:
+            rb = getattr(enc, "last_bufs", None) or enc.rd_bufs
+            dump_payloads(args.dump_outputs, [(disp, stype, qp)] * B, [read_payload(hip, rb, enc.payload_cap, b) for b in range(B)])
+        else:                                        # no entropy coding in this variant: its product is the decision arrays of the state
+            names = ("mb_type", "partition", "sub_partition", "ref", "mv", "qp", "cbp")
+            per = sum(state.get(k)[0].size for k in names) * 4
+            pick = np.sort(dump_order(B)[:max(1, min(B, (DUMP_BYTES - 8 * B) // per))])
+            arrs = {"state_" + k: state.get(k)[pick].astype(np.float32) for k in names}
+            arrs["state_chains"] = pick.astype(np.float64)
+            save_dump(args.dump_outputs, arrs)
 
     # the dominant kernel (k_slice_sweep), timed live with HIP events on its launch stream: every launch of the timed region
     # (P launches with 1..R references, B launches, and the I launch at the keyint), so that the mean is the one rocprofv3's kernel

@@ -45,18 +45,22 @@ OURS = {
 }
 
 
-@need_ref
 @pytest.mark.parametrize("name", sorted(CLI))
 def test_param2string_equals_the_references(hip_lib_host, name):
-    from oracle import hostpic
-    ref = hostpic.load_lazy(REF_SO)
-    ref.x264_param2string.restype = C.c_void_p
-    buf = C.create_string_buffer(16384)
-    ref.x264_param_default(buf)
-    for k, v in CLI[name]:
-        assert ref.x264_param_parse(buf, k.encode(), None if v is None else v.encode()) == 0, (k, v)
-    ptr = ref.x264_param2string(buf, 0)
-    want = C.string_at(ptr).decode()
+    """Where oracle/_ref is not built: the reference's string as tests/golden/ref_offline.npz holds it (oracle/gen_golden_ref_offline.py)."""
+    if os.path.exists(REF_SO):
+        from oracle import hostpic
+        ref = hostpic.load_lazy(REF_SO)
+        ref.x264_param2string.restype = C.c_void_p
+        buf = C.create_string_buffer(16384)
+        ref.x264_param_default(buf)
+        for k, v in CLI[name]:
+            assert ref.x264_param_parse(buf, k.encode(), None if v is None else v.encode()) == 0, (k, v)
+        ptr = ref.x264_param2string(buf, 0)
+        want = C.string_at(ptr).decode()
+    else:
+        with np.load(os.path.join(ROOT, "tests", "golden", "ref_offline.npz")) as g:
+            want = str(g["p2s_mux_%s" % name])
     p = mux.encoder_params(hip_lib_host, validate=False, width=352, height=288, **OURS[name])
     assert mux.param2string(hip_lib_host, p) == want
 

@@ -5,7 +5,8 @@ the main encode.  No GPU: the per-frame costs the decisions read come from the o
 pins at the same time; tests/test_gpu_lookahead.py then holds the kernel to the oracle.
 
   * golden: tests/golden/look_host.npz, made by oracle/gen_golden_look.py from the reference (runs everywhere);
-  * live: further seeds against oracle/_ref/libx264ref.so where it is built."""
+  * live: further seeds against oracle/_ref/libx264ref.so where it is built, and where it is not against the same runs of the reference as
+    tests/golden/ref_offline.npz holds them (oracle/gen_golden_ref_offline.py)."""
 import os
 
 import numpy as np
@@ -20,6 +21,23 @@ from x264_vs2008_amd import lookahead as LA
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 REF_SO = os.path.join(ROOT, "oracle", "_ref", "libx264ref.so")
 GOLD = np.load(os.path.join(ROOT, "tests", "golden", "look_host.npz"))
+FIXTURE = os.path.join(ROOT, "tests", "golden", "ref_offline.npz")
+LIVE_SEEDS = list(range(200, 236))
+POST_SEEDS = [11, 13, 14, 15, 19, 20, 26, 36, 37, 201, 208, 209, 214, 226, 229]
+
+
+def stored_records(g, prefix):
+    """Records of the reference's run in the layout of look_host.npz (oracle/gen_golden_look.py)."""
+    head, qavg, mv = g[prefix + "_head"], g[prefix + "_qavg"], g[prefix + "_mv"]
+    return [dict(frame=int(h[0]), slice=int(h[1]), poc=int(h[2]), qp=int(h[3]), satd=int(h[4]), f_qp_avg=float(q),
+                 mv0=m[0] if h[5] else None, mv1=m[1] if h[6] else None) for h, q, m in zip(head, qavg, mv)]
+
+
+def post_config(seed):
+    c = dict(K.config(seed), pre_scenecut=0)
+    if c["scenecut_threshold"] < 0:
+        c["scenecut_threshold"] = 40
+    return c
 
 
 def run_mine(c, log=None, speculative=True):
@@ -32,38 +50,39 @@ def run_mine(c, log=None, speculative=True):
 @pytest.mark.parametrize("seed", [int(s) for s in GOLD["seeds"]])
 def test_host_lookahead_equals_reference_fixture(seed):
     c = K.config(seed)
-    head, qavg, mv = GOLD["s%d_head" % seed], GOLD["s%d_qavg" % seed], GOLD["s%d_mv" % seed]
-    ref = [dict(frame=int(h[0]), slice=int(h[1]), poc=int(h[2]), qp=int(h[3]), satd=int(h[4]), f_qp_avg=float(q),
-                mv0=m[0] if h[5] else None, mv1=m[1] if h[6] else None) for h, q, m in zip(head, qavg, mv)]
-    bad = K.compare(run_mine(c), ref)
+    bad = K.compare(run_mine(c), stored_records(GOLD, "s%d" % seed))
     assert not bad, "%s: %s" % (c, bad[:5])
 
 
-@pytest.mark.skipif(not os.path.exists(REF_SO), reason="oracle/_ref/libx264ref.so not built (needs /root/reference)")
-@pytest.mark.parametrize("seed", list(range(200, 236)))
+@pytest.mark.parametrize("seed", LIVE_SEEDS)
 def test_host_lookahead_equals_reference_live(seed):
     c = K.config(seed)
-    ref = K.records_of_reference(K.reference_records(c), c["frames"])
+    if os.path.exists(REF_SO):
+        ref = K.records_of_reference(K.reference_records(c), c["frames"])
+    else:
+        with np.load(FIXTURE) as g:
+            ref = stored_records(g, "live%d" % seed)
     bad = K.compare(run_mine(c), ref)
     assert not bad, "%s: %s" % (c, bad[:5])
 
 
-@pytest.mark.skipif(not os.path.exists(REF_SO), reason="oracle/_ref/libx264ref.so not built (needs /root/reference)")
-@pytest.mark.parametrize("seed", [11, 13, 14, 15, 19, 20, 26, 36, 37, 201, 208, 209, 214, 226, 229])
+@pytest.mark.parametrize("seed", POST_SEEDS)
 def test_host_post_encode_scenecut_equals_reference_live(seed):
     """Without --pre-scenecut: the reference's run tells which attempts its post-encode scene cut gave up (refslice_out.stat[..][3]); with the same
     verdicts x264hip_lookahead_scenecut must rearrange the queues, re-type the pictures and run the rate control (x264_ratecontrol_start twice for
     a picture coded twice) exactly as x264_encoder_encode does (encoder.c:1645-1699): order, types, QPs, i_satd, the vectors offered to the encode."""
-    c = dict(K.config(seed), pre_scenecut=0)
-    if c["scenecut_threshold"] < 0:
-        c["scenecut_threshold"] = 40
-    a = K.reference_records(c)
-    give = [int(a["stat"][f][3]) for f in range(c["frames"])]
+    c = post_config(seed)
+    if os.path.exists(REF_SO):
+        a = K.reference_records(c)
+        give, want = [int(a["stat"][f][3]) for f in range(c["frames"])], K.records_of_reference(a, c["frames"])
+    else:
+        with np.load(FIXTURE) as g:
+            give, want = [int(x) for x in g["post%d_give" % seed]], stored_records(g, "post%d" % seed)
     lib = L.open_library()
     y, u, v = K.clip(c["w"], c["h"], c["frames"], c["cut"], c["t0"], c["slow"])
     look = U.CpuLook(lib, c["w"], c["h"], c["me"], 16, c["weightb"], c["bframe_bias"], c["bframes"])
     mine = U.run_chain(lib, K.lookahead_params(c), look, y, u, v, c["frames"], giveups=give)
-    bad = K.compare(mine, K.records_of_reference(a, c["frames"]))
+    bad = K.compare(mine, want)
     assert not bad, "%s (given up: %s): %s" % (c, give, bad[:5])
     assert sum(give) > 0
 
