@@ -66,6 +66,7 @@ void  x264hip_host_free(void *host);
 int   x264hip_memcpy_d2h_async(void *dst_host, const void *src_dev, size_t bytes, void *hip_stream);
 int   x264hip_memcpy_h2d_async(void *dst_dev, const void *src_host, size_t bytes, void *hip_stream);
 int   x264hip_mem_info(size_t *free_bytes, size_t *total_bytes);      /* hipMemGetInfo of the library's device */
+int   x264hip_device_cus(void);      /* compute units of the library's device (after x264hip_init); -1 on error */
 void *x264hip_stream_create(void);
 void  x264hip_stream_destroy(void *hip_stream);
 int   x264hip_stream_synchronize(void *hip_stream);
@@ -140,7 +141,8 @@ int x264hip_picture_upload_async(x264hip_frame_ctx *c, x264hip_picture *pic, con
                                  const uint8_t *v, int sv, void *hip_stream);
 /* synthetic source: batch element b becomes frame t0 + b * t_stride of the integer-only test clip (the generator of
  * x264_vs2008_amd/synth.py, bit for bit), padded to the coded size; asynchronous on the context's stream.  Benchmarks take their input
- * from here, so every (chain, frame) is a picture of its own and no upload is involved. */
+ * from here, so every (chain, frame) is a picture of its own and no upload is involved.  Returns -1 (nothing launched) when
+ * t0 + (batch - 1) * t_stride exceeds INT_MAX. */
 int x264hip_picture_synth(x264hip_frame_ctx *c, x264hip_picture *pic, int t0, int t_stride);
 int x264hip_picture_download(x264hip_frame_ctx *c, const x264hip_picture *pic, int plane_id /*0..2 Y,U,V; 3..5 H,V,HV; 6..9 lowres*/,
                              uint8_t *dst, int dst_stride, int with_padding);

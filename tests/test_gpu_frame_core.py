@@ -107,11 +107,50 @@ def test_aq_var_and_ssd(ctx, hip_lib, oracle_lib):
 def test_synthetic_source_on_the_device_equals_the_host_generator(hip_lib, size, batch):
     """x264hip_picture_synth (the bench's input: SURVEY 8(d)'s integer generator as a kernel) against x264_vs2008_amd/synth.py,
     every visible pixel and the mod-16 padding, for several batch elements with their own frame numbers."""
+    _synth_equals_host(hip_lib, size, batch, 37, 12)
+
+
+INT_MAX = (1 << 31) - 1
+
+
+# bench.py's frame numbers: chain g's pictures start g * 4096 frames into the clip, so with 8 GPUs of 2048 chains the last chain's reach
+# (7 * 2048 + 2047) * 4096 ~ 6.7e7 (weak scaling, stride 4096; strong scaling: rank + 8 * b, stride 8 * 4096) -- where (x + y + 5t) * 9 no
+# longer fits an int; and the largest frame number the library accepts
+@pytest.mark.parametrize("size,t0,ts", [((1920, 1080), (7 * 2048 + 2045) * 4096 + 15, 4096), ((200, 120), (7 + 8 * 2045) * 4096 + 4095, 8 * 4096),
+                                         ((352, 288), INT_MAX - 2 * 1000003, 1000003), ((200, 120), INT_MAX - 2, 1)])
+def test_synthetic_source_at_the_benchmarks_frame_numbers(hip_lib, size, t0, ts):
+    _synth_equals_host(hip_lib, size, 3, t0, ts)
+
+
+def test_synthetic_source_refuses_frame_numbers_above_int_max(hip_lib):
+    """t0 + (batch - 1) * t_stride > INT_MAX: an error, and nothing is written; the last legal frame number is synthesised right."""
+    from x264_vs2008_amd import synth
+    c = FrameCtx(hip_lib, 200, 120, batch=3)
+    try:
+        pic = c.new_picture(source_only=True)
+        c.synth(pic, 5, 7)
+        c.sync()
+        before = [c.download(pic, name, padded=True, b=b) for b in range(3) for name in ("y", "u", "v")]
+        for t0, ts in ((INT_MAX - 2 * 4096 + 1, 4096), (1, INT_MAX), (INT_MAX, 1), (2, (1 << 30))):
+            with pytest.raises(RuntimeError, match="exceeds INT_MAX"):
+                c.synth(pic, t0, ts)
+        c.sync()
+        after = [c.download(pic, name, padded=True, b=b) for b in range(3) for name in ("y", "u", "v")]
+        assert all(np.array_equal(a, b) for a, b in zip(before, after)), "a refused x264hip_picture_synth wrote the picture"
+        c.synth(pic, INT_MAX - 2 * 4096, 4096)                   # element 2: frame INT_MAX
+        c.sync()
+        for name, pl in zip(("y", "u", "v"), synth.frame(200, 120, INT_MAX)):
+            got = c.download(pic, name, padded=False, b=2)
+            _eq(got[:pl.shape[0], :pl.shape[1]], pl, "synth %s element 2 (frame INT_MAX)" % name)
+    finally:
+        c.close()
+
+
+def _synth_equals_host(hip_lib, size, batch, t0, ts):
     from x264_vs2008_amd import synth
     c = FrameCtx(hip_lib, *size, batch=batch)
     try:
         pic = c.new_picture(source_only=True)
-        t0, ts = 37, 12
         c.synth(pic, t0, ts)
         c.sync()
         w, h = size
@@ -120,7 +159,7 @@ def test_synthetic_source_on_the_device_equals_the_host_generator(hip_lib, size,
             for name, pl in zip(("y", "u", "v"), want):
                 got = c.download(pic, name, padded=False, b=b)
                 hh, ww = pl.shape
-                _eq(got[:hh, :ww], pl, "synth %s element %d" % (name, b))
+                _eq(got[:hh, :ww], pl, "synth %s element %d (frame %d)" % (name, b, t0 + b * ts))
                 # x264_frame_expand_border_mod16: the last column / row repeated up to the coded size
                 assert (got[:hh, ww:] == pl[:, -1:]).all() and (got[hh:, :ww] == pl[-1:, :]).all() and (got[hh:, ww:] == pl[-1, -1]).all()
     finally:

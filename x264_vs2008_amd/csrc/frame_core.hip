@@ -11,6 +11,7 @@
 // picture; stride_y = ALIGN(16*mb_w + 64, 16).  Pointers in x264hip_picture
 // address pixel (0,0).  All kernels are HBM-bound byte streams: coalesced
 // dword / 16-byte accesses, LDS only where a tile is reused (the 6-tap filter).
+#include <climits>
 #include <cstdlib>
 #include <cstring>
 #include "device_prims.h"
@@ -34,8 +35,10 @@ __global__ void k_pad_mod16(u8 *p, int stride, int w, int h, int w16, int h16)
 // The integer-only synthetic I420 source of SURVEY.md 8(d) (x264_vs2008_amd/synth.py is the same generator on the host): a smooth
 // translating texture, a moving 64x64 box and +-3 LSB hash noise, uint32 wrap-around arithmetic.  Frame index of batch element b is
 // t0 + b * t_stride, so every (chain, display index) of a benchmark run is a picture of its own.  One dword (4 pixels) per thread;
-// columns / rows beyond the visible picture replicate its last column / row (x264_frame_expand_border_mod16).
-__device__ __forceinline__ int synth_tri(int v) { const int a = v & 255; return a < 128 ? a - 64 : 191 - a; }
+// columns / rows beyond the visible picture replicate its last column / row (x264_frame_expand_border_mod16).  The benchmark's frame numbers reach
+// ~6.7e7 (chain g starts g * 4096 frames into the clip), so the triangle waves' arguments wrap in u32 (only their low 8 bits count) and the box
+// position's remainders are taken in 64 bits; x264hip_picture_synth refuses frame numbers above INT_MAX.
+__device__ __forceinline__ int synth_tri(u32 v) { const int a = (int)(v & 255u); return a < 128 ? a - 64 : 191 - a; }
 __device__ __forceinline__ int synth_noise(u32 x, u32 y, u32 t, u32 p, int amp)
 {
     u32 h = x * 73856093u ^ y * 19349663u ^ t * 83492791u ^ p * 2654435761u ^ 1234u;
@@ -47,19 +50,22 @@ __global__ __launch_bounds__(256) void k_synth_plane(u8 *pix, size_t bs, int str
 {
     const int xq = (blockIdx.x * blockDim.x + threadIdx.x) * 4, yy = blockIdx.y;
     if (xq >= w16) return;
-    const int t = t0 + (int)blockIdx.z * t_stride, y = yy < h ? yy : h - 1;
+    const long long t64 = (long long)t0 + (long long)blockIdx.z * t_stride;       // <= INT_MAX (checked by the caller)
+    const u32 t = (u32)t64;
+    const int y = yy < h ? yy : h - 1;
     u32 out = 0;
 #pragma unroll
     for (int i = 0; i < 4; i++) {
         const int x = xq + i < w ? xq + i : w - 1;
+        const u32 ux = (u32)x, uy = (u32)y;
         int v;
         if (plane == 0) {
-            v = 128 + (synth_tri((x + 3 * t) * 4) >> 1) + (synth_tri((y - 2 * t) * 6) >> 2) + (synth_tri((x + y + 5 * t) * 9) >> 3);
-            const int bx = (40 + 7 * t) % (full_w - 64), by = (30 + 3 * t) % (full_h - 64);
-            if (x >= bx && x < bx + 64 && y >= by && y < by + 64) v += synth_tri(x * 16) >> 1;
-            v += synth_noise((u32)x, (u32)y, (u32)t, 0, 3);
-        } else if (plane == 1) v = 128 + (synth_tri((x + 2 * t) * 3) >> 2) + synth_noise((u32)x, (u32)y, (u32)t, 1, 1);
-        else v = 128 + (synth_tri((y - t) * 5) >> 2) + synth_noise((u32)x, (u32)y, (u32)t, 2, 1);
+            v = 128 + (synth_tri((ux + 3u * t) * 4u) >> 1) + (synth_tri((uy - 2u * t) * 6u) >> 2) + (synth_tri((ux + uy + 5u * t) * 9u) >> 3);
+            const int bx = (int)((40 + 7 * t64) % (full_w - 64)), by = (int)((30 + 3 * t64) % (full_h - 64));
+            if (x >= bx && x < bx + 64 && y >= by && y < by + 64) v += synth_tri(ux * 16u) >> 1;
+            v += synth_noise(ux, uy, t, 0, 3);
+        } else if (plane == 1) v = 128 + (synth_tri((ux + 2u * t) * 3u) >> 2) + synth_noise(ux, uy, t, 1, 1);
+        else v = 128 + (synth_tri((uy - t) * 5u) >> 2) + synth_noise(ux, uy, t, 2, 1);
         out |= (u32)clip_u8(v) << (8 * i);
     }
     *(u32 *)(pix + bs * blockIdx.z + (size_t)yy * stride + xq) = out;
@@ -406,6 +412,10 @@ extern "C" int x264hip_picture_synth(x264hip_frame_ctx *c, x264hip_picture *pic,
 {
     const x264hip_frame_dims &d = c->d;
     if (d.width < 65 || d.height < 65 || t0 < 0 || t_stride < 0) { set_error("picture_synth: needs a picture larger than 64x64 and non-negative frame numbers"); return -1; }
+    if ((long long)t0 + (long long)(c->batch - 1) * t_stride > INT_MAX) {
+        set_error("picture_synth: frame number t0 + (batch - 1) * t_stride = %lld exceeds INT_MAX", (long long)t0 + (long long)(c->batch - 1) * t_stride);
+        return -1;
+    }
     for (int i = 0; i < 3; i++) {
         const int w = d.width >> !!i, h = d.height >> !!i, st = i ? d.stride_c : d.stride_y, w16 = c->width16 >> !!i, h16 = c->lines16 >> !!i;
         hipLaunchKernelGGL(k_synth_plane, dim3((w16 / 4 + 255) / 256, h16, c->batch), dim3(256), 0, c->stream, pic->plane[i], i ? c->bs_c : c->bs_y, st, i, w, h, w16, h16,

@@ -80,6 +80,14 @@ extern "C" int x264hip_device_count(void)
     return n;
 }
 
+extern "C" int x264hip_device_cus(void)
+{
+    if (!initialised()) { set_error("x264hip_device_cus: call x264hip_init first"); return -1; }
+    int n = 0;
+    HIPCHK(hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, g_device));
+    return n;
+}
+
 extern "C" int x264hip_init(const x264hip_cfg *cfg)
 {
     int n = 0;
