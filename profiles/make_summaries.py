@@ -12,6 +12,17 @@ def sweeps(db, what):
     return list(c.execute(what))
 
 
+def sweep_kind(name):
+    """"B" for the B-slice kernel (template argument BS), "P" for the I / P kernel (whose launches also carry a step's I chains), from
+    the demangled name rocpd stores ("k_slice_sweep<2, false, true, true, true, false, true>") or the mangled one (..ILi2ELb0ELb1ELb1E..)."""
+    if "k_slice_sweep<" in name:
+        args = [a.strip() for a in name.split("k_slice_sweep<", 1)[1].split(">", 1)[0].split(",")]
+    else:
+        args = ["true" if a == "1" else "false" for a in name.split("ILi", 1)[1].split("EEv", 1)[0].split("ELb")[1:]]
+        args = ["wpe"] + args
+    return "B" if len(args) > 3 and args[3] == "true" else "P"
+
+
 if sys.argv[1] == "stream":
     # the stream mode: per step the I / P table kernel and the B table kernel side by side on two streams, and the lookahead's cost kernels
     db, bench, stats, out = sys.argv[2:6]
@@ -24,7 +35,7 @@ if sys.argv[1] == "stream":
     rows = list(c.execute("select start, end, name, grid_x from kernels where name like '%k_slice_sweep%' order by start"))
     steps = []
     for s_, e_, name, gx in rows:
-        kind = "B" if "ELb1ELb1ELb1ELb0ELb1EEv" in name else "IP"
+        kind = sweep_kind(name)
         if steps and s_ < steps[-1]["end"]:
             steps[-1]["end"] = max(steps[-1]["end"], e_)
         else:

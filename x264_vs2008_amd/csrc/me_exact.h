@@ -892,3 +892,276 @@ __device__ __forceinline__ int me_refine_qpel16(const MxCtx &c_in, const MeLimit
     mvx = bx; mvy = by;
     return bc;
 }
+
+// ---- one 8x8 block against up to four references at once ------------------------------------------------------------------
+// x264_mb_analyse_inter_p8x8_mixed_ref searches a block once per reference, and the searches do not depend on each other.  A
+// serial 8x8 search keeps most of the wave idle (a full-pel trip fills 8 of every 16 lanes, a sub-pel trip 4), so here each
+// reference gets a SLOT of 16 lanes (one DPP row, lanes 16 s .. 16 s + 15) and every trip scores all slots' candidates together:
+//   * full-pel and predictor trips: 8 candidates per slot, 2 lanes each, 4 picture rows per lane;
+//   * half-pel trips: 4 candidates per slot, 4 lanes each, 2 rows per lane;
+//   * sub-pel (mbcmp) trips: 4 candidates per slot, 4 units each: the two 8x4 luma blocks, U, V.
+// A slot's walk is me_search_ref16's for that reference alone (same candidates in the same order, key = cost << 3 | candidate,
+// strict '<', the hexagon's early exits, INRANGE, the L.smax1 clamp, cost_mv); its state lives in VGPRs, equal across the slot.
+// Control flow stays wave-uniform: a loop runs while any live slot goes on, and a slot that has stopped recomputes the
+// candidates around its final position (which its own walk read already) without taking them.  Every lane holds one plane
+// pointer of its slot's reference (lane j < 6: the four half-pel planes, U, V at the block), fetched by ds_bpermute when used:
+// two VGPRs instead of six 64-bit pointers per slot.  Sub-pel reads go to global memory (the staged patch holds one reference).
+// Only X264_ME_HEX at subme >= 3 without a threshold (what the P 8x8 analysis uses); every other case keeps me_search_ref16.
+__device__ __forceinline__ u32 mr_row_min16(u32 v)
+{
+    v = min(v, (u32)dpp_mov<0x128>((int)v)); v = min(v, (u32)dpp_mov<0x124>((int)v));      // row_ror 8, 4, 2, 1
+    v = min(v, (u32)dpp_mov<0x122>((int)v)); v = min(v, (u32)dpp_mov<0x121>((int)v));
+    return v;
+}
+__device__ __forceinline__ int mr_from(int v, int src) { return __builtin_amdgcn_ds_bpermute(src << 2, v); }
+// plane k (0-3 half-pel, 4 U, 5 V) of the reference of the slot whose first lane is sb
+__device__ __forceinline__ MX_GLB(u8) mr_plane(uint64_t plv, int sb, int k)
+{
+    const u32 lo = (u32)mr_from((int)(u32)plv, sb + k), hi = (u32)mr_from((int)(u32)(plv >> 32), sb + k);
+    return (MX_GLB(u8))(((uint64_t)hi << 32) | lo);
+}
+// per-lane mv cost of the quarter-pel vector (qx, qy) against the lane's predictor (MxCtx::lane_cost with a lane-varying predictor)
+__device__ __forceinline__ int mr_cost(const MxCtx &c, int qx, int qy, int mvpx, int mvpy)
+{
+    const int dx = qx - mvpx, dy = qy - mvpy;
+    const bool in = c.has_cost_l && (unsigned)(dx + MX_COST_LDS) <= 2u * MX_COST_LDS && (unsigned)(dy + MX_COST_LDS) <= 2u * MX_COST_LDS;
+    if (__ballot(!in) == 0) return (int)c.cost_l[dx + MX_COST_LDS] + (int)c.cost_l[dy + MX_COST_LDS];
+    return (int)c.cost_g[dx] + (int)c.cost_g[dy];
+}
+// SAD of NR rows (from row0) of the 8x8 block's quarter-pel candidate (qx, qy) through get_ref's blend, for this lane alone
+template <int NR> __device__ __forceinline__ int mr_sad_rows(const MxCtx &c, uint64_t plv, int sb, int qx, int qy, int row0)
+{
+    const int fx = qx & 3, fy = qy & 3, idx = fy * 4 + fx;
+    const ptrdiff_t base = (ptrdiff_t)((qy >> 2) + row0) * c.sy + (qx >> 2);
+    MX_GLB(u8) pa = mr_plane(plv, sb, c_qpel_a[idx]) + base + (fy == 3) * c.sy;
+    MX_GLB(u8) pb = mr_plane(plv, sb, c_qpel_b[idx]) + base + (fx == 3);
+    u32 s = 0;
+#pragma unroll
+    for (int y = 0; y < NR; y++) {
+        u32 a0, a1, t;
+        load9u(pa + (ptrdiff_t)y * c.sy, a0, a1, t);
+        if (idx & 5) { u32 b0, b1; load9u(pb + (ptrdiff_t)y * c.sy, b0, b1, t); a0 = avg4(a0, b0); a1 = avg4(a1, b1); }
+        MX_LDS(u32) f = c.fe + c.fe_off + 4 * (row0 + y);
+        s = sad4(a0, f[0], s); s = sad4(a1, f[1], s);
+    }
+    return (int)s;
+}
+// COST_MV_SATD's sum of the 8x8 block's candidate (qx, qy) without the mv cost, 4 lanes per candidate (subpel_sum16_lane's units
+// for an 8x8 block: u = 0, 1 luma 8x4 at rows 0 / 4, u = 2 U, u = 3 V, 4x4 each); the sum is in all four lanes
+__device__ __forceinline__ int mr_subpel_sum4(const MxCtx &c, uint64_t plv, int sb, int qx, int qy, int satd, int chroma, int u)
+{
+    int v = 0;
+    u32 d[4][4];
+    bool have_d = false;
+    // the planes first, in every lane: a permute from a lane that a branch has switched off reads zero
+    const int fx = qx & 3, fy = qy & 3, idx = fy * 4 + fx;
+    MX_GLB(u8) qa = mr_plane(plv, sb, u < 2 ? (int)c_qpel_a[idx] : u + 2);
+    MX_GLB(u8) qb = mr_plane(plv, sb, c_qpel_b[idx]);
+    if (u < 2) {
+        const int by = 4 * u;
+        const ptrdiff_t base = (ptrdiff_t)((qy >> 2) + by) * c.sy + (qx >> 2);
+        MX_GLB(u8) pa = qa + base + (fy == 3) * c.sy;
+        MX_GLB(u8) pb = qb + base + (fx == 3);
+        u32 f[4][2], p[4][2];
+#pragma unroll
+        for (int y = 0; y < 4; y++) {
+            u32 t;
+            load9u(pa + (ptrdiff_t)y * c.sy, p[y][0], p[y][1], t);
+            if (idx & 5) {
+                u32 b0, b1;
+                load9u(pb + (ptrdiff_t)y * c.sy, b0, b1, t);
+                p[y][0] = avg4(p[y][0], b0); p[y][1] = avg4(p[y][1], b1);
+            }
+            f[y][0] = c.fe[c.fe_off + (by + y) * 4]; f[y][1] = c.fe[c.fe_off + (by + y) * 4 + 1];
+        }
+        if (satd) {
+#pragma unroll
+            for (int y = 0; y < 4; y++)
+#pragma unroll
+                for (int x = 0; x < 4; x++) d[y][x] = mx_pair(f[y][1], f[y][0], x) - mx_pair(p[y][1], p[y][0], x);
+            have_d = true;
+        } else v = blk8x4_cost(f, p, 0);
+    } else if (chroma) {
+        MX_GLB(u8) plane = qa;
+        MX_LDS(u8) fe = (u == 2 ? c.fe_u : c.fe_v) + c.cfe_off;
+        const int dx = qx & 7, dy = qy & 7;
+        const int ca = (8 - dx) * (8 - dy), cb = dx * (8 - dy), cc = (8 - dx) * dy, cd = dx * dy;
+        MX_GLB(u8) s = plane + (ptrdiff_t)(qy >> 3) * c.sc + (qx >> 3);
+        u32 r0[5], r1[5], r2[5];
+#pragma unroll
+        for (int y = 0; y < 5; y++) load9u(s + (ptrdiff_t)y * c.sc, r0[y], r1[y], r2[y]);
+        if (satd) {
+            u32 a[5][5];
+#pragma unroll
+            for (int y = 0; y < 5; y++) {
+#pragma unroll
+                for (int x = 0; x < 4; x++) a[y][x] = mx_pair(r1[y], r0[y], x);
+                a[y][4] = mx_pair(r2[y], r1[y], 0);
+            }
+            const mx_u16x2 ka = {(unsigned short)ca, (unsigned short)ca}, kb = {(unsigned short)cb, (unsigned short)cb};
+            const mx_u16x2 kc = {(unsigned short)cc, (unsigned short)cc}, kd = {(unsigned short)cd, (unsigned short)cd}, k32 = {32, 32};
+#pragma unroll
+            for (int y = 0; y < 4; y++) {
+                MX_LDS(u32) fr = (MX_LDS(u32))(fe + y * 8);
+                const u32 f0 = fr[0], f1 = fr[1];
+#pragma unroll
+                for (int x = 0; x < 4; x++) {
+                    const mx_u16x2 pv = (mx_as_pk(a[y][x]) * ka + mx_as_pk(a[y][x + 1]) * kb + mx_as_pk(a[y + 1][x]) * kc + mx_as_pk(a[y + 1][x + 1]) * kd + k32) >> 6;
+                    d[y][x] = (mx_pair(f1, f0, x) & 0xffffu) - (mx_as_u32(pv) & 0xffffu);      // 4-wide: the right half contributes nothing
+                }
+            }
+            have_d = true;
+        } else {
+            u32 f[4][2], p[4][2];
+#pragma unroll
+            for (int y = 0; y < 4; y++) {
+                u32 w0 = 0;
+#pragma unroll
+                for (int x = 0; x < 4; x++) {
+                    const int a0 = byte_of(r0[y], x), a1 = x < 3 ? byte_of(r0[y], x + 1) : byte_of(r1[y], 0);
+                    const int b0 = byte_of(r0[y + 1], x), b1 = x < 3 ? byte_of(r0[y + 1], x + 1) : byte_of(r1[y + 1], 0);
+                    w0 |= (u32)((ca * a0 + cb * a1 + cc * b0 + cd * b1 + 32) >> 6) << (8 * x);
+                }
+                p[y][0] = w0; f[y][0] = ((MX_LDS(u32))(fe + y * 8))[0];
+                p[y][1] = 0u; f[y][1] = 0u;
+            }
+            v = blk8x4_cost(f, p, 0);
+        }
+    }
+    if (have_d) v = satd8x4_packed(d);
+    return quad_sum4(v);
+}
+
+// x264_me_search_ref (hex, subme >= 3, no threshold) of the 8x8 block c is set to, once per slot.  Per lane, equal across its
+// slot: the slot's predictor (mvpx, mvpy), its candidate list mvc (n_mvc <= 7 entries, LDS), live (false: a spare slot, whose
+// walk does not hold the others up and whose result is not used) and plv (see above: lane j < 6 of the slot holds plane j of the
+// slot's reference at the block).  Returns m->cost without the reference cost; out_* as me_search_ref16's.
+__device__ __forceinline__ int me_search_refs8(const MxCtx &c_in, uint64_t plv, const MeLimits &L_in, const MeOpts &o_in, MX_LDS(i16) mvc, int n_mvc,
+                                               bool live, int mvpx, int mvpy, int &out_mvx, int &out_mvy, int &out_cost_mv)
+{
+    MxCtx c = c_in;
+    c.cost_g = mx_uni_ptr(c_in.cost_g); c.sy = MX_UNI(c_in.sy); c.sc = MX_UNI(c_in.sc); c.fe_off = MX_UNI(c_in.fe_off); c.cfe_off = MX_UNI(c_in.cfe_off);
+    const MeLimits L = mx_uniform(L_in);
+    const MeOpts o = mx_uniform(o_in);
+    n_mvc = MX_UNI(n_mvc);
+    const int j = c.lane & 15, sb = c.lane & 48, k8 = j >> 1, k4 = j >> 2;
+    const int satd = !o.sad_only;                                               // subme > 1 here
+#define INRANGE(x_, y_) ((x_) >= L.fmin0 && (x_) <= L.fmax0 && (y_) >= L.fmin1 && (y_) <= L.fmax1)
+    // the candidates of a trip with 2 (SH 1) or 4 (SH 2) lanes each: the slot's smallest key, and the (x, y) of its candidate
+#define MR_KEY(SH_, cost_, ok_) mr_row_min16((ok_) ? ((u32)(cost_) << 3) | (u32)(j >> (SH_)) : 0xffffffffu)
+#define MR_TAKE(SH_, key_, live_, bcost_, x_, y_, bx_, by_) do { const int l_ = sb + ((int)((key_) & 7u) << (SH_)); \
+        const int tx_ = mr_from((x_), l_), ty_ = mr_from((y_), l_); \
+        if ((live_) && ((key_) >> 3) < (u32)(bcost_)) { (bcost_) = (int)((key_) >> 3); (bx_) = tx_; (by_) = ty_; } } while (0)
+    int bmx = clip3(mvpx, L.fmin0 * 4, L.fmax0 * 4), bmy = clip3(mvpy, L.fmin1 * 4, L.fmax1 * 4);
+    int bcost = MX_COST_MAX, bpx = 0, bpy = 0, bpcost = MX_COST_MAX;
+    {
+        // me.c:188-210: the predictor and every distinct non-zero candidate at quarter-pel precision (SAD), one trip
+        const int px = bmx, py = bmy;
+        int x = px, y = py;
+        bool ok = k8 == 0;
+        if (k8 >= 1 && k8 <= n_mvc) {
+            const int vx = (int)mvc[2 * (k8 - 1)], vy = (int)mvc[2 * (k8 - 1) + 1];
+            if ((vx | vy) && (vx != (int)(i16)px || vy != (int)(i16)py)) {
+                ok = true; x = clip3(vx, L.fmin0 * 4, L.fmax0 * 4); y = clip3(vy, L.fmin1 * 4, L.fmax1 * 4);
+            }
+        }
+        int sad = mr_sad_rows<4>(c, plv, sb, x, y, 4 * (j & 1));
+        sad += dpp_mov<DPP_XOR1>(sad);
+        const u32 key = MR_KEY(1, sad + mr_cost(c, x, y, mvpx, mvpy), ok);
+        MR_TAKE(1, key, true, bpcost, x, y, bpx, bpy);
+    }
+    bmx = (bpx + 2) >> 2; bmy = (bpy + 2) >> 2;
+    {
+        // COST_MV(bmx, bmy); COST_MV(0, 0)
+        const int x = k8 == 0 ? bmx : 0, y = k8 == 0 ? bmy : 0;
+        int sad = mr_sad_rows<4>(c, plv, sb, x << 2, y << 2, 4 * (j & 1));
+        sad += dpp_mov<DPP_XOR1>(sad);
+        const u32 key = MR_KEY(1, sad + mr_cost(c, x << 2, y << 2, mvpx, mvpy), k8 < 2);
+        MR_TAKE(1, key, true, bcost, x, y, bmx, bmy);
+    }
+    {
+        // hexagon, me.c:246-305: the first ring hex2[1..6], then three candidates per step
+        int dir = -2;
+        {
+            const int hi = (k8 < 6 ? k8 : 0) + 1;
+            const int x = bmx + mx_nib(MX_HEX2_DX, hi), y = bmy + mx_nib(MX_HEX2_DY, hi);
+            int sad = mr_sad_rows<4>(c, plv, sb, x << 2, y << 2, 4 * (j & 1));
+            sad += dpp_mov<DPP_XOR1>(sad);
+            const u32 key = MR_KEY(1, sad + mr_cost(c, x << 2, y << 2, mvpx, mvpy), k8 < 6);
+            if ((key >> 3) < (u32)bcost) { bcost = (int)(key >> 3); dir = (int)(key & 7u); }
+        }
+        const int hex_steps = o.me_range / 2;
+        bool go = dir != -2;
+        if (go) { bmx += mx_nib(MX_HEX2_DX, dir + 1); bmy += mx_nib(MX_HEX2_DY, dir + 1); }
+        int i = 1;
+        go = go && i < hex_steps && INRANGE(bmx, bmy);
+        while (__ballot(go && live)) {
+            const int odir = dir + 1 >= 7 ? dir - 6 : dir + 1 <= 0 ? dir + 6 : dir;                 // mod6m1[dir + 1]
+            const int idx = odir + (k8 < 3 ? k8 : 0);
+            const int x = bmx + mx_nib(MX_HEX2_DX, idx), y = bmy + mx_nib(MX_HEX2_DY, idx);
+            int sad = mr_sad_rows<4>(c, plv, sb, x << 2, y << 2, 4 * (j & 1));
+            sad += dpp_mov<DPP_XOR1>(sad);
+            const u32 key = MR_KEY(1, sad + mr_cost(c, x << 2, y << 2, mvpx, mvpy), k8 < 3);
+            if (go) {
+                if ((key >> 3) >= (u32)bcost) go = false;
+                else {
+                    bcost = (int)(key >> 3); dir = odir - 1 + (int)(key & 7u);
+                    bmx += mx_nib(MX_HEX2_DX, dir + 1); bmy += mx_nib(MX_HEX2_DY, dir + 1);
+                    i++;
+                    go = i < hex_steps && INRANGE(bmx, bmy);
+                }
+            }
+        }
+        // square refine around the hexagon's best, me.c:300-304
+        const int x = bmx + mx_nib(MX_NIB8(0, 0, -1, 1, -1, -1, 1, 1), k8), y = bmy + mx_nib(MX_NIB8(-1, 1, 0, 0, -1, 1, -1, 1), k8);
+        int sad = mr_sad_rows<4>(c, plv, sb, x << 2, y << 2, 4 * (j & 1));
+        sad += dpp_mov<DPP_XOR1>(sad);
+        const u32 key = MR_KEY(1, sad + mr_cost(c, x << 2, y << 2, mvpx, mvpy), true);
+        MR_TAKE(1, key, true, bcost, x, y, bmx, bmy);
+    }
+    int bx, by, bc;
+    if (bpcost < bcost) { bx = bpx; by = bpy; bc = bpcost; }
+    else { bx = bmx << 2; by = bmy << 2; bc = bcost; }
+    // refine_subpel(.., b_refine_qpel = 0), me.c:680-778
+    const int hpel = c_subpel_iters[o.subme][2], qpel = c_subpel_iters[o.subme][3];
+    {
+        bool go = hpel > 0;
+        int it = hpel;
+        while (__ballot(go && live)) {
+            const int ox = bx, oy = by;
+            const int x = ox + 2 * mx_nib(MX_DIA_DX, k4), y = oy + 2 * mx_nib(MX_DIA_DY, k4);
+            const int sad = quad_sum4(mr_sad_rows<2>(c, plv, sb, x, y, 2 * (j & 3)));
+            const u32 key = MR_KEY(2, sad + mr_cost(c, x, y, mvpx, mvpy), true);
+            MR_TAKE(2, key, go, bc, x, y, bx, by);
+            if (go) go = --it > 0 && (bx != ox || by != oy);
+        }
+    }
+    if (by > L.smax1) by = L.smax1;
+    bc = mr_subpel_sum4(c, plv, sb, bx, by, satd, o.chroma_me, j & 3) + mr_cost(c, bx, by, mvpx, mvpy);
+    {
+        int bdir = -1, it = qpel;
+        bool go = qpel > 0;
+        while (__ballot(go && live)) {
+            const int ox = bx, oy = by, odir = bdir;
+            const int x = ox + mx_nib(MX_DIA_DX, k4), y = oy + mx_nib(MX_DIA_DY, k4);
+            const int cost = mr_subpel_sum4(c, plv, sb, x, y, satd, o.chroma_me, j & 3) + mr_cost(c, x, y, mvpx, mvpy);
+            const u32 key = MR_KEY(2, cost, (k4 ^ 1) != odir);               // the direction just come from is not tried again
+            const bool win = go && (key >> 3) < (u32)bc;
+            MR_TAKE(2, key, go, bc, x, y, bx, by);
+            if (win) bdir = (int)(key & 7u);
+            if (go) go = --it > 0 && (bx != ox || by != oy);
+        }
+    }
+    const bool clamp = by > L.smax1;
+    if (__ballot(clamp && live)) {
+        if (clamp) by = L.smax1;
+        const int cost = mr_subpel_sum4(c, plv, sb, bx, by, satd, o.chroma_me, j & 3) + mr_cost(c, bx, by, mvpx, mvpy);
+        if (clamp) bc = cost;
+    }
+    out_cost_mv = mr_cost(c, bx, by, mvpx, mvpy);                                  // me.c:777
+#undef MR_TAKE
+#undef MR_KEY
+#undef INRANGE
+    out_mvx = bx; out_mvy = by;
+    return bc;
+}

@@ -2130,9 +2130,44 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE))) void 
                                 maxref = max(maxref, __builtin_amdgcn_readlane(cref_v, 3)); maxref = max(maxref, __builtin_amdgcn_readlane(cref_v, 4)); maxref = max(maxref, __builtin_amdgcn_readlane(cref_v, 6));
                                 maxref = max(maxref, __builtin_amdgcn_readlane(cref_v, 8)); maxref = max(maxref, __builtin_amdgcn_readlane(cref_v, 11)); maxref = max(maxref, __builtin_amdgcn_readlane(cref_v, 27));
                             }
+                            bool multi = false;                      // every reference's search of a block at once (me_search_refs8)
+                            if constexpr (RD && !BS) multi = maxref > 0 && mo.method == 1 && mo.subme >= 3;
                             for (int i = 0; i < 4; i++) {
                                 int bcost = 0x7fffffff, bvx = 0, bvy = 0, bcm = 0, br = 0, bpx = 0, bpy = 0;
-                                for (int r = 0; r <= maxref; r++) {
+                                const int bx8 = 8 * (i & 1), by8 = 8 * (i >> 1);
+                                for (int r0 = 0; multi && r0 <= maxref; r0 += 4) {      // four references (slots of 16 lanes) per pass
+                                    const int nsl = min(maxref - r0 + 1, 4), slot = lane >> 4, j = lane & 15;
+                                    // every reference's predictor first: x264_mb_predict_mv with only the block's cached reference changed.
+                                    // A spare slot repeats the pass's first reference.
+                                    int lpx = 0, lpy = 0;
+                                    for (int t = 0; t < nsl; t++) {
+                                        cache_set(2 * (i & 1), 2 * (i >> 1), 2, 2, r0 + t, 0, 0, 0);
+                                        int px, py;
+                                        predict_blk(13, 4 * i, 2, px, py);
+                                        if (slot == t || (t == 0 && slot >= nsl)) { lpx = px; lpy = py; }
+                                    }
+                                    const bool live = slot < nsl;
+                                    const int r = r0 + (live ? slot : 0);
+                                    // lane j < 6 of a slot: plane j of its reference at the block (four half-pel planes, U, V)
+                                    const u8 *pb = j < 4 ? refs.y[r][j & 3] : j == 4 ? refs.u[r] : refs.v[r];
+                                    const uint64_t plv = j < 4 ? (uint64_t)(uintptr_t)(pb + by_ + oy + (ptrdiff_t)by8 * a.sy + bx8)
+                                                               : (uint64_t)(uintptr_t)(pb + bc_ + oc + (ptrdiff_t)(by8 >> 1) * a.sc + (bx8 >> 1));
+                                    c.set_block(8, 8, bx8, by8);
+                                    int vx, vy, cm;
+                                    LAUNDER(); c.lane = lane;
+                                    const int cost = me_search_refs8(c, plv, L, mo, (MX_LDS(i16))&s.l0mvc[r][0][0], i + 1, live, lpx, lpy, vx, vy, cm);
+                                    for (int t = 0; t < nsl; t++) {                  // the winner in reference order, strict '<'
+                                        const int rt = r0 + t, ct = __builtin_amdgcn_readlane(cost, 16 * t) + (Q.lambda * refs.ref_bits[rt]);
+                                        const int tvx = __builtin_amdgcn_readlane(vx, 16 * t), tvy = __builtin_amdgcn_readlane(vy, 16 * t);
+                                        if (lane == 0) { s.l0mvc[rt][i + 1][0] = (i16)tvx; s.l0mvc[rt][i + 1][1] = (i16)tvy; }
+                                        if (ct < bcost) {
+                                            bcost = ct; bvx = tvx; bvy = tvy; bcm = __builtin_amdgcn_readlane(cm, 16 * t); br = rt;
+                                            bpx = __builtin_amdgcn_readlane(lpx, 16 * t); bpy = __builtin_amdgcn_readlane(lpy, 16 * t);
+                                        }
+                                    }
+                                    WAVE_SYNC();
+                                }
+                                for (int r = 0; !multi && r <= maxref; r++) {
                                     cache_set(2 * (i & 1), 2 * (i >> 1), 2, 2, r, 0, 0, 0);
                                     int px, py, vx, vy, cm;
                                     predict_blk(13, 4 * i, 2, px, py);
