@@ -21,6 +21,15 @@ def _declared_functions(path):
     return sorted(set(n for n in names if not n.endswith("_t")))
 
 
+def _declared_non_int(path):
+    """The functions a header declares with a return type other than int / void."""
+    src = open(path).read()
+    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
+    src = re.sub(r"typedef\s+struct\s*\{.*?\}\s*\w+\s*;", "", src, flags=re.S)
+    decls = re.findall(r"([\w \t\*]+?)\b(x264(?:hip)?_\w+)\s*\(", src)
+    return sorted(set(n for ret, n in decls if not n.endswith("_t") and " ".join(ret.split()) not in ("int", "void")))
+
+
 def test_library_exports_every_declared_symbol():
     from x264_vs2008_amd import lib as L
     if not os.path.exists(L.SO_PATH):
@@ -31,6 +40,11 @@ def test_library_exports_every_declared_symbol():
         assert len(declared) > (30 if header == "x264hip.h" else 8)
         missing = [n for n in declared if not hasattr(lib, n)]
         assert not missing, "declared in include/%s but not exported: %s" % (header, missing)
+        # ctypes takes every function to return int: one that returns a pointer, a size_t or a float needs its restype declared by open_library()
+        other = _declared_non_int(os.path.join(ROOT, "include", header))
+        assert header != "x264hip.h" or len(other) > 10
+        default = [n for n in other if getattr(lib, n).restype is C.c_int]
+        assert not default, "declared in include/%s with a return type other than int / void, restype left at the default: %s" % (header, default)
 
 
 def test_lookahead_struct_sizes_match_header():
@@ -84,7 +98,9 @@ def test_table_struct_sizes_match_header():
 #include "x264hip.h"
 int main(void){ printf("%zu %zu %zu %zu %zu %zu %zu %zu %zu\n", sizeof(x264hip_pixel_function_t), sizeof(x264hip_dct_function_t),
  sizeof(x264hip_zigzag_function_t), sizeof(x264hip_quant_function_t), sizeof(x264hip_mc_functions_t),
- sizeof(x264hip_deblock_function_t), sizeof(x264hip_run_level_t), sizeof(x264hip_picture), sizeof(x264hip_me_params)); return 0; }
+ sizeof(x264hip_deblock_function_t), sizeof(x264hip_run_level_t), sizeof(x264hip_picture), sizeof(x264hip_me_params));
+ printf("%zu %zu %zu %zu %zu %zu\n", sizeof(x264hip_mb_state), sizeof(x264hip_slice_params), sizeof(x264hip_slice_rd), sizeof(x264hip_slice_b),
+ sizeof(x264hip_nr_state), sizeof(x264hip_deblock_params)); return 0; }
 '''
     exe = os.path.join(ROOT, "tests", "_sizes.bin")
     subprocess.run(["gcc", "-x", "c", "-", "-I", os.path.join(ROOT, "include"), "-o", exe], input=prog.encode(), check=True)
@@ -92,10 +108,12 @@ int main(void){ printf("%zu %zu %zu %zu %zu %zu %zu %zu %zu\n", sizeof(x264hip_p
         got = [int(v) for v in subprocess.check_output([exe]).split()]
     finally:
         os.remove(exe)
-    from x264_vs2008_amd.frame import MeParams, Picture
+    from x264_vs2008_amd.frame import DeblockParams, MeParams, Picture
+    from x264_vs2008_amd.slice import MbState, NrState, SliceB, SliceParams, SliceRd
     want = [C.sizeof(T.PixelTable), C.sizeof(T.DctTable), C.sizeof(T.ZigzagTable), C.sizeof(T.QuantTable), C.sizeof(T.McTable),
-            C.sizeof(T.DeblockTable), C.sizeof(T.RunLevel), C.sizeof(Picture), C.sizeof(MeParams)]
-    assert got == want
+            C.sizeof(T.DeblockTable), C.sizeof(T.RunLevel), C.sizeof(Picture), C.sizeof(MeParams),
+            C.sizeof(MbState), C.sizeof(SliceParams), C.sizeof(SliceRd), C.sizeof(SliceB), C.sizeof(NrState), C.sizeof(DeblockParams)]
+    assert got == want, (got, want)
 
 
 def test_cost_mv_table_properties():

@@ -57,7 +57,6 @@ class DeviceArray:
     def __init__(self, lib, shape, dtype, init=None):
         self.lib, self.shape, self.dtype = lib, tuple(np.atleast_1d(shape)), np.dtype(dtype)
         self.nbytes = int(np.prod(self.shape)) * self.dtype.itemsize
-        lib.x264hip_malloc.restype = C.c_void_p
         self.ptr = lib.x264hip_malloc(C.c_size_t(self.nbytes))
         if not self.ptr:
             raise MemoryError("x264hip_malloc(%d) failed" % self.nbytes)
@@ -92,8 +91,6 @@ class FrameCtx:
 
     def __init__(self, lib, width, height, stream=None, batch=1):
         self.lib = lib
-        lib.x264hip_frame_ctx_new.restype = C.c_void_p
-        lib.x264hip_frame_ctx_stream.restype = C.c_void_p
         self.batch = batch
         self.dims = Dims(width=width, height=height, batch=batch)
         self.h = lib.x264hip_frame_ctx_new(C.byref(self.dims), C.c_void_p(stream))
@@ -168,6 +165,10 @@ class FrameCtx:
         if self.h:
             self.lib.x264hip_frame_ctx_delete(self.h)
             self.h = None
+
+
+LAMBDA_TAB = (1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 2, 2, 2, 2, 3, 3, 3, 4, 4, 4, 5, 6,
+              6, 7, 8, 9, 10, 11, 13, 14, 16, 18, 20, 23, 25, 29, 32, 36, 40, 45, 51, 57, 64, 72, 81, 91)   # x264_lambda_tab, R/encoder/analyse.c:140-149
 
 
 def chroma_qp(qp, offset=0):

@@ -20,6 +20,19 @@ class Cfg(C.Structure):
     _fields_ = [("device", C.c_int), ("arena_bytes", C.c_size_t)]
 
 
+# The prototypes ctypes cannot guess (it assumes int everywhere): the return type of every exported function that does not return int, and the
+# argument types of every function that takes a float by value.  Declared here once, for every user of the library.
+RESTYPES = {
+    C.c_char_p: ("x264hip_last_error",),
+    C.c_float: ("x264hip_event_elapsed_ms",),
+    C.c_size_t: ("x264hip_lookahead_state_bytes", "x264hip_lookahead_task_bytes", "x264hip_chain_sweep_bytes"),
+    C.c_void_p: ("x264hip_malloc", "x264hip_host_alloc", "x264hip_stream_create", "x264hip_stream_create_high_priority",
+                 "x264hip_stream_create_cu_range", "x264hip_event_create", "x264hip_frame_ctx_new", "x264hip_frame_ctx_stream",
+                 "x264hip_lookahead_new"),
+}
+ARGTYPES = {"x264hip_adaptive_quant_frame": (C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p)}
+
+
 def build(verbose=False):
     """Compile csrc/*.hip for gfx950 into libx264hip.so (in-tree)."""
     cmd = ["make", "-C", os.path.join(_HERE, "csrc"), "-j8"]
@@ -39,11 +52,15 @@ def build_examples():
 
 
 def open_library():
-    """dlopen only (no device needed): used to check exported symbols."""
+    """dlopen only (no device needed), with the prototypes of RESTYPES / ARGTYPES declared."""
     if not os.path.exists(SO_PATH):
         raise X264HipError("libx264hip.so not built: run `python -c 'import __graft_entry__ as g; g.build()'`")
     lib = C.CDLL(SO_PATH)
-    lib.x264hip_last_error.restype = C.c_char_p
+    for restype, names in RESTYPES.items():
+        for name in names:
+            getattr(lib, name).restype = restype
+    for name, argtypes in ARGTYPES.items():
+        getattr(lib, name).argtypes = argtypes
     return lib
 
 

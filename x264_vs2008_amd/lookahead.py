@@ -54,26 +54,15 @@ class Frame(C.Structure):
 
 
 def bind(lib):
-    lib.x264hip_lookahead_new.restype = C.c_void_p
-    lib.x264hip_lookahead_new.argtypes = [C.POINTER(LookaheadParams)]
-    lib.x264hip_lookahead_delete.argtypes = [C.c_void_p]
-    lib.x264hip_lookahead_put.argtypes = [C.c_void_p]
-    lib.x264hip_lookahead_get.argtypes = [C.c_void_p, C.c_int, C.POINTER(Frame), C.POINTER(Need), C.c_int, C.POINTER(C.c_int)]
-    lib.x264hip_lookahead_set_cost.argtypes = [C.c_void_p] + [C.c_int] * 7
-    lib.x264hip_lookahead_end.argtypes = [C.c_void_p]
-    lib.x264hip_lookahead_scenecut.argtypes = [C.c_void_p]
-    lib.x264hip_lookahead_state_bytes.restype = C.c_size_t
-    lib.x264hip_lookahead_save.argtypes = [C.c_void_p, C.c_void_p]
-    lib.x264hip_lookahead_restore.argtypes = [C.c_void_p, C.c_void_p]
-    lib.x264hip_lookahead_oldest_live.argtypes = [C.c_void_p]
+    """Nothing left to do: lib.open_library() declares the prototypes that matter.  Kept for its callers."""
     return lib
 
 
 class Lookahead:
     def __init__(self, lib, params):
-        self.lib = bind(lib)
+        self.lib = lib
         self.params = params
-        self.h = lib.x264hip_lookahead_new(C.byref(params))
+        self.h = C.c_void_p(lib.x264hip_lookahead_new(C.byref(params)))      # as a pointer: a bare integer would be passed on as a C int
         if not self.h:
             raise ValueError("x264hip_lookahead_new refused the parameters (bframes > 16, unknown rate control, ...)")
         self._need = (Need * MAX_NEED)()
@@ -187,9 +176,7 @@ class LookaheadDevice:
         self.cost_mv = DeviceArray(lib, tab.shape, np.int16, tab)
         self.params = LookParams(me_method, me_range, weightb, bframes, bframe_bias, subme, lossless, self.cost_mv.ptr, COST_SPAN)
         self.max_tasks = max_tasks or 8 * ctx.batch
-        lib.x264hip_lookahead_task_bytes.restype = C.c_size_t
         tb = lib.x264hip_lookahead_task_bytes()
-        lib.x264hip_host_alloc.restype = C.c_void_p
         self.staging = lib.x264hip_host_alloc(C.c_size_t(tb * self.max_tasks))
         self.tasks_dev = DeviceArray(lib, (tb * self.max_tasks,), np.uint8)
         self.out_dev = DeviceArray(lib, (self.max_tasks, 4), np.int32)
@@ -246,7 +233,6 @@ class LookaheadDevice:
         np, ctx, lib = self.np, self.ctx, self.lib
         assert 0 < len(tasks) <= self.max_tasks
         if not hasattr(self, "_ring"):
-            lib.x264hip_event_create.restype = C.c_void_p
             tb = lib.x264hip_lookahead_task_bytes()
             self._ring = [dict(staging=lib.x264hip_host_alloc(C.c_size_t(tb * self.max_tasks)), out=lib.x264hip_host_alloc(C.c_size_t(16 * self.max_tasks)),
                                ev=lib.x264hip_event_create(), busy=False) for _ in range(16)]

@@ -44,7 +44,6 @@ class SliceHeader(C.Structure):
 
 
 def _err(lib):
-    lib.x264hip_last_error.restype = C.c_char_p
     return (lib.x264hip_last_error() or b"").decode()
 
 

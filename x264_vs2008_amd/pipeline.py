@@ -22,10 +22,8 @@ import ctypes as C
 
 import numpy as np
 
-from .frame import (CqmDevice, DeblockParams, DeviceArray, FrameCtx, MeParams, chroma_qp, cost_mv_table)
+from .frame import (LAMBDA_TAB, CqmDevice, DeblockParams, DeviceArray, FrameCtx, MeParams, chroma_qp, cost_mv_table)
 
-LAMBDA_TAB = (1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 2, 2, 2, 2, 3, 3, 3, 4, 4, 4, 5, 6,
-              6, 7, 8, 9, 10, 11, 13, 14, 16, 18, 20, 23, 25, 29, 32, 36, 40, 45, 51, 57, 64, 72, 81, 91)
 COST_SPAN = 4 * 2048          # the reference's p_cost_mv span: +-2*4*2048 qpel (analyse.c:191-198); half is ample here
 
 
@@ -106,5 +104,4 @@ class PFramePass:
 
 
 def setup_event_api(lib):
-    lib.x264hip_event_create.restype = C.c_void_p
-    lib.x264hip_event_elapsed_ms.restype = C.c_float
+    """Nothing left to do: lib.open_library() declares the event functions' return types.  Kept for its callers."""

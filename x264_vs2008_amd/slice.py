@@ -10,12 +10,10 @@ import math
 
 import numpy as np
 
-from .frame import CqmDevice, DeblockParams, DeviceArray, FrameCtx
+from .frame import LAMBDA_TAB, CqmDevice, DeblockParams, DeviceArray, FrameCtx
 
 SLICE_P, SLICE_B, SLICE_I = 0, 1, 2
 I_4x4, I_8x8, I_16x16, I_PCM, P_L0, P_8x8, P_SKIP = range(7)
-LAMBDA_TAB = (1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 2, 2, 2, 2, 3, 3, 3, 4, 4, 4, 5, 6,
-              6, 7, 8, 9, 10, 11, 13, 14, 16, 18, 20, 23, 25, 29, 32, 36, 40, 45, 51, 57, 64, 72, 81, 91)   # R/encoder/analyse.c:140-149
 COST_SPAN = 2 * 4 * 2048      # p_cost_mv reaches +-2*4*2048 quarter-pels (R/encoder/analyse.c:191-198)
 
 STATE_FIELDS = [("mb_type", np.int8, ()), ("partition", np.int8, ()), ("sub_partition", np.int8, (4,)), ("ref", np.int8, (4,)), ("i4mode", np.int8, (16,)),
@@ -183,15 +181,14 @@ class ChainEncoder:
             rb["unquant4_mf"] = DeviceArray(lib, u4.shape, np.int32, u4)
             rb["unquant8_mf"] = DeviceArray(lib, u8.shape, np.int32, u8)
             # x264hip_slice_rd.stale: the motion-cache entry that survives macroblocks and frames (read when temporal direct prediction
-            # fails); one record per chain, zero like the reference's freshly allocated x264_t
+            # fails); one record per chain, zero like the reference's freshly allocated x264_t.  Per chain, and a chain's frames stay in
+            # order, so temporal direct prediction also goes with the encoder that lets the chains drift apart (AsyncStreamEncoder)
             rb["stale"] = DeviceArray(lib, (B, 8), np.int16)
             self.rd_bufs = rb
             self.payload_cap = cap
         if self.cavlc and not levels:
             raise ValueError("CAVLC payloads are written from the coefficient levels: levels=False does not go with cabac=0, write=1")
         if self.cavlc and not self.raster:
-            if not levels:
-                raise ValueError("CAVLC payloads are written from the coefficient levels: levels=False does not go with cabac=0, write=1")
             d = self.ctx.dims
             n = d.mb_w * d.mb_h
             self.payload_cap = payload_cap or (n * 800 + MB_BYTES_MAX + 128 + PAYLOAD_LEAD)
@@ -211,7 +208,7 @@ class ChainEncoder:
         if not levels and not self.rd_opt["write"]:
             raise ValueError("levels=False: the coefficient levels are the only product unless the sweep writes the payload (write=1)")
         self.states = [DeviceState(self.ctx, levels) for _ in range(self.dpb + 1)]
-        self.refs = []                 # [(picture, state, poc)], newest first
+        self.refs = []                 # [(picture, state, poc)], newest first (StreamEncoder.crefs: the same fields per chain)
         # lanes: the B frames between two anchors predict from the anchors only, never from each other, so they are independent
         # of one another and of the NEXT anchor.  With lanes = K each B frame is enqueued on one of K extra streams (own
         # reconstruction, state and payload buffers), ordered behind the anchor it needs by an event, and runs beside the
@@ -235,8 +232,6 @@ class ChainEncoder:
         if noise_reduction:
             self.nr = NrState()
             self.ctx.check(lib.x264hip_nr_state_alloc(self.ctx.h, C.byref(self.nr)), "nr_state_alloc")
-        lib.x264hip_event_create.restype = C.c_void_p
-        lib.x264hip_event_elapsed_ms.restype = C.c_float
 
     def _frame_bufs(self, B, n, cap, aq_mode):
         """What one frame in flight writes: the payload, its length, the bit position after every macroblock, the AQ arrays."""
@@ -270,6 +265,50 @@ class ChainEncoder:
         for ln in self.lanes:          # a B frame still in flight on a lane may be reading this picture
             ln["ctx"].sync()
         self.ctx.upload(self.fenc, y, u, v, b=b)
+
+    # ---- the records a sweep is given: built here for every encoder of this package --------------------------------------------------
+    def ref_lists(self, refs, poc, stype):
+        """x264_reference_build_list (R/encoder/encoder.c:911-981) over [(picture, state, poc, ...)]: list 0 = earlier pictures, nearest
+        first; list 1 = later ones."""
+        l0 = sorted([r for r in refs if r[2] < poc], key=lambda r: -r[2])[:self.opt["n_refs"]] if stype != SLICE_I else []
+        l1 = sorted([r for r in refs if r[2] > poc], key=lambda r: r[2])[:1] if stype == SLICE_B else []
+        return l0, l1
+
+    def slice_params(self, stype, qp, poc, cost_mv, lowres_mv):
+        """x264hip_slice_params.  cost_mv: device address of p_cost_mv for this QP; lowres_mv: device address of the lookahead's vectors
+        ([batch][n_mb][2] int16) or None.  ref_poc, rd and b are the caller's to fill."""
+        o, b = self.opt, self.cqm.bufs
+        return SliceParams(slice_type=stype, qp=qp, chroma_qp_offset=o["chroma_qp_offset"], me_method=o["me_method"], me_range=o["me_range"],
+                           subme=o["subme"], chroma_me=o["chroma_me"], mv_range=o["mv_range"] or 512, fast_pskip=o["fast_pskip"], dct_decimate=o["dct_decimate"],
+                           cabac=o["cabac"], transform8x8=o["transform8x8"], analyse_inter=o["inter"], analyse_intra=o["intra"],
+                           quant4_mf=b["quant4_mf"].ptr, quant4_bias=b["quant4_bias"].ptr, quant8_mf=b["quant8_mf"].ptr,
+                           quant8_bias=b["quant8_bias"].ptr, dequant4_mf=b["dequant4_mf"].ptr, dequant8_mf=b["dequant8_mf"].ptr,
+                           cost_mv=cost_mv, cost_mv_range=COST_SPAN, poc=poc, mixed_refs=o["mixed_refs"],
+                           profile=self.profile.ptr if self.profile else None,
+                           noise_reduction=o["noise_reduction"], nr=C.addressof(self.nr) if self.nr else None, lossless=self.lossless,
+                           lowres_mv=lowres_mv)
+
+    def slice_rd(self, rb, f_qpm, i_frame, aq_offset, write, i_frame_stride):
+        """x264hip_slice_rd for a frame that writes into the buffer set rb (_frame_bufs + the tables of rd_bufs).  aq_offset: device address
+        of the frame's AQ offsets or None."""
+        ro = self.rd_opt
+        return SliceRd(trellis=ro["trellis"], psy_rd=self.psy_rd_fix, write=write, cabac_init_idc=ro["cabac_init_idc"], i_frame=i_frame,
+                       qp_min=ro["qp_min"], qp_max=ro["qp_max"], f_qpm=f_qpm, aq_offset=aq_offset,
+                       cost_mv_all=rb["cost_mv_all"].ptr, unquant4_mf=rb["unquant4_mf"].ptr, unquant8_mf=rb["unquant8_mf"].ptr,
+                       payload=rb["payload"].ptr, payload_cap=self.payload_cap, payload_len=rb["payload_len"].ptr, mb_bits=rb["mb_bits"].ptr,
+                       stale=rb["stale"].ptr, i_frame_stride=i_frame_stride)
+
+    def filter_kept(self, c, recon, s):
+        """x264_fdec_filter_row for a whole kept frame, enqueued on context c: loop filter (from the x264hip_mb_state s), borders, half-pel
+        planes."""
+        L, o = self.lib, self.opt
+        if o["deblock"]:
+            dp = DeblockParams(mb_type=s.mb_type, qp=s.qp, nnz=s.nnz, transform8x8=s.t8, mv=s.mv, ref=s.ref,
+                               alpha_c0_offset=o["alpha_c0"], beta_offset=o["beta"], chroma_qp_offset=o["chroma_qp_offset"], state_layout=1,
+                               sub8x8=1 if o["inter"] & 0x20 else 0)
+            c.check(L.x264hip_deblock_frame(c.h, C.byref(recon), C.byref(dp)), "deblock_frame")
+        c.check(L.x264hip_expand_border(c.h, C.byref(recon), 0), "expand_border")
+        c.check(L.x264hip_hpel_filter_frame(c.h, C.byref(recon)), "hpel_filter_frame")
 
     def encode_frame(self, src=None, stype=None, disp=None, lowres_mv=None, lowres_mv1=None):
         """The macroblock sweep for the frame held by `src` (default: the picture upload() fills) in every
@@ -306,33 +345,16 @@ class ChainEncoder:
                 else:
                     L.x264hip_event_destroy(C.c_void_p(ev))
             self.b_readers = keep
-        # x264_reference_build_list (R/encoder/encoder.c:911-981): list 0 = earlier pictures, nearest first; list 1 = later ones
-        refs = sorted([r for r in self.refs if r[2] < poc], key=lambda r: -r[2])[:o["n_refs"]]
-        refs1 = sorted([r for r in self.refs if r[2] > poc], key=lambda r: r[2])[:1] if is_b else []
+        refs, refs1 = self.ref_lists(self.refs, poc, stype)
         qp = iframe_qp(o["qp"]) if idr else bframe_qp(o["qp"]) if is_b else o["qp"]
         self.last_is_b, self.last_poc = is_b, poc
-        b = self.cqm.bufs
-        p = SliceParams(slice_type=stype, qp=qp, chroma_qp_offset=o["chroma_qp_offset"], me_method=o["me_method"], me_range=o["me_range"],
-                        subme=o["subme"], chroma_me=o["chroma_me"], mv_range=o["mv_range"] or 512, fast_pskip=o["fast_pskip"], dct_decimate=o["dct_decimate"],
-                        cabac=o["cabac"], transform8x8=o["transform8x8"], analyse_inter=o["inter"], analyse_intra=o["intra"],
-                        quant4_mf=b["quant4_mf"].ptr, quant4_bias=b["quant4_bias"].ptr, quant8_mf=b["quant8_mf"].ptr,
-                        quant8_bias=b["quant8_bias"].ptr, dequant4_mf=b["dequant4_mf"].ptr, dequant8_mf=b["dequant8_mf"].ptr,
-                        cost_mv=self.cost_table(qp).ptr, cost_mv_range=COST_SPAN, poc=poc, mixed_refs=o["mixed_refs"],
-                        profile=self.profile.ptr if self.profile else None,
-                        noise_reduction=o["noise_reduction"], nr=C.addressof(self.nr) if self.nr else None, lossless=self.lossless,
-                        lowres_mv=lowres_mv.ptr if lowres_mv is not None else None)        # DeviceArray [batch][n_mb][2] int16: the lookahead's vectors
+        p = self.slice_params(stype, qp, poc, self.cost_table(qp).ptr, lowres_mv.ptr if lowres_mv is not None else None)
         if self.raster:
             rb, ro = dict(self.rd_bufs, **lane["bufs"]) if lane else self.rd_bufs, self.rd_opt
             self.last_bufs = rb
             if ro["aq_mode"]:                  # x264_adaptive_quant_frame on the source (R/encoder/encoder.c:1421)
-                L.x264hip_adaptive_quant_frame.argtypes = [C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p]
                 c.check(L.x264hip_adaptive_quant_frame(c.h, C.byref(fenc), C.c_float(ro["aq_strength"]), rb["aq_energy"].p, rb["aq_offset"].p), "adaptive_quant_frame")
-            self.rd = SliceRd(trellis=ro["trellis"], psy_rd=self.psy_rd_fix, write=ro["write"], cabac_init_idc=ro["cabac_init_idc"], i_frame=self.i_frame,
-                              qp_min=ro["qp_min"], qp_max=ro["qp_max"], f_qpm=float(qp), aq_offset=rb["aq_offset"].ptr if ro["aq_mode"] else None,
-                              cost_mv_all=rb["cost_mv_all"].ptr, unquant4_mf=rb["unquant4_mf"].ptr, unquant8_mf=rb["unquant8_mf"].ptr,
-                              payload=rb["payload"].ptr, payload_cap=self.payload_cap, payload_len=rb["payload_len"].ptr, mb_bits=rb["mb_bits"].ptr,
-                              stale=rb["stale"].ptr,
-                              i_frame_stride=self.i_frame_stride)
+            self.rd = self.slice_rd(rb, float(qp), self.i_frame, rb["aq_offset"].ptr if ro["aq_mode"] else None, ro["write"], self.i_frame_stride)
             p.rd = C.addressof(self.rd)
         if is_b:
             self.sb = SliceB(fref1=C.addressof(refs1[0][0]), l1_state=C.addressof(refs1[0][1].st), ref1_poc=refs1[0][2],
@@ -378,14 +400,7 @@ class ChainEncoder:
             self.t += 1
             self.i_frame += 1
             return
-        if o["deblock"]:
-            s = state.st
-            dp = DeblockParams(mb_type=s.mb_type, qp=s.qp, nnz=s.nnz, transform8x8=s.t8, mv=s.mv, ref=s.ref,
-                               alpha_c0_offset=o["alpha_c0"], beta_offset=o["beta"], chroma_qp_offset=o["chroma_qp_offset"], state_layout=1,
-                               sub8x8=1 if o["inter"] & 0x20 else 0)
-            c.check(L.x264hip_deblock_frame(c.h, C.byref(recon), C.byref(dp)), "deblock_frame")
-        c.check(L.x264hip_expand_border(c.h, C.byref(recon), 0), "expand_border")
-        c.check(L.x264hip_hpel_filter_frame(c.h, C.byref(recon)), "hpel_filter_frame")
+        self.filter_kept(c, recon, state.st)
         self.refs.insert(0, (recon, state, getattr(self, "last_poc", 2 * (self.t - self.last_idr))))
         del self.refs[self.dpb:]
         if self.lanes:                         # the point the B frames that predict from this anchor wait for

@@ -20,8 +20,8 @@ import sys
 import numpy as np
 
 from . import lookahead as LA
-from .frame import DeblockParams, DeviceArray
-from .slice import (COST_SPAN, ChainEncoder, MbState, SLICE_B, SLICE_I, SLICE_P, SliceB, SliceParams, SliceRd)
+from .frame import DeviceArray
+from .slice import COST_SPAN, ChainEncoder, MbState, SLICE_B, SLICE_I, SLICE_P, SliceB
 
 
 class ChainSweep(C.Structure):
@@ -65,7 +65,6 @@ class StreamEncoder(ChainEncoder):
         # b_cus: the step's B kernel on compute units [0, b_cus), its I / P kernel (and everything else of this context) on the rest
         self._cu_streams = []
         if b_cus:
-            lib.x264hip_stream_create_cu_range.restype = C.c_void_p
             sb_, sp_ = lib.x264hip_stream_create_cu_range(0, b_cus), lib.x264hip_stream_create_cu_range(b_cus, 256 - b_cus)
             if not sb_ or not sp_:
                 raise RuntimeError("x264hip_stream_create_cu_range failed")
@@ -79,7 +78,6 @@ class StreamEncoder(ChainEncoder):
             self.ctx.check(lib.x264hip_frame_ctx_set_b_stream(self.ctx.h, C.c_void_p(sb_)), "frame_ctx_set_b_stream")
         self._hp_stream = None
         if lookahead_priority:
-            lib.x264hip_stream_create_high_priority.restype = C.c_void_p
             self._hp_stream = lib.x264hip_stream_create_high_priority()
         self.src_ctx = FrameCtx(lib, width, height, stream=self._hp_stream, batch=batch)
         self.n_frames = n_frames
@@ -93,12 +91,11 @@ class StreamEncoder(ChainEncoder):
         self.aq_slots = None
         if self.rd_opt["aq_mode"]:
             self.aq_slots = [(DeviceArray(lib, (B, n), np.int32), DeviceArray(lib, (B, n), np.float32)) for _ in range(self.n_slots)]
-        # per chain: [(pool index, poc, MbState copy with this chain's frame-level scalars)], newest first; the IDR's input number; frames coded
+        # per chain: [(picture, MbState copy with this chain's frame-level scalars, poc, pool index)], newest first (ChainEncoder.refs' fields
+        # and the pool index); the IDR's input number; frames coded
         self.crefs = [[] for _ in range(B)]
         self.c_last_idr = [0] * B
         self.c_coded = [0] * B
-        lib.x264hip_chain_sweep_bytes.restype = C.c_size_t
-        lib.x264hip_host_alloc.restype = C.c_void_p
         tb = lib.x264hip_chain_sweep_bytes()
         self.tab_host = lib.x264hip_host_alloc(C.c_size_t(tb * B))
         self.tab_dev = DeviceArray(lib, (tb * B,), np.uint8)
@@ -216,8 +213,7 @@ class StreamEncoder(ChainEncoder):
 
     def _sweep(self, frames):
         """The chain-table launch for the chains that have a frame in `frames` (per chain an x264hip_look_frame or None), then the filters of the kept ones."""
-        L, c, o, ro = self.lib, self.ctx, self.opt, self.rd_opt
-        B = c.batch
+        L, c = self.lib, self.ctx
         todo = [(ci, fr) for ci, fr in enumerate(frames) if fr is not None]
         if self._dscore_pending:                        # the B frames of the last sweep: their skip sums join the running scores before the next mode is picked
             c.sync()
@@ -228,51 +224,14 @@ class StreamEncoder(ChainEncoder):
                     sc[0], sc[1] = sc[0] * 9 // 10, sc[1] * 9 // 10
                 sc[0] += int(fs[ci][0]); sc[1] += int(fs[ci][1])
             self._dscore_pending = []
-        keep = []                                       # everything the C call reads must outlive it
-        entries = (ChainSweep * len(todo))()
-        b = self.cqm.bufs
-        rb = self.rd_bufs
-        written, filt = set(), {}
-        out = []
-        for k, (ci, fr) in enumerate(todo):
-            entries[k], cd, pic_i = self._entry(ci, fr, keep)
-            written.add(pic_i)
-            out.append(cd)
-            if cd.slice_type != SLICE_B:                   # kept: filtered below
-                filt.setdefault(pic_i, []).append(ci)
-        c.sync()                                        # the previous step's sweep and filters are done: their tables, element lists and pictures are free
-        for pic_i in written:
-            c.check(L.x264hip_mb_state_clear_progress(c.h, C.byref(self.states[pic_i].st)), "mb_state_clear_progress")
-        ev = None
-        if self.sweep_events is not None:
-            ev = (L.x264hip_event_create(), L.x264hip_event_create())
-            L.x264hip_event_record(C.c_void_p(ev[0]), C.c_void_p(c.stream))
-        c.check(L.x264hip_slice_sweep_chains(c.h, entries, len(todo), C.c_void_p(self.tab_host), self.tab_dev.p), "slice_sweep_chains")
+        # (c.sync: the previous step's sweep and filters are done: their tables, element lists and pictures are free)
+        out, keep, filt, ev = self._launch(c, todo, C.c_void_p(self.tab_host), self.tab_dev.p, self._publish_elements, c.sync)
         if ev:
-            L.x264hip_event_record(C.c_void_p(ev[1]), C.c_void_p(c.stream))
             px = self.ctx.dims.mb_w * 16 * self.ctx.dims.lines_y
             # per frame the source (1.5 B/px), each reference's four luma planes + chroma (4.5 B/px) and the reconstruction (1.5 B/px)
             self.sweep_events.append((ev[0], ev[1], len(todo), sum(px * (3.0 + 4.5 * (cd.n_ref0 + cd.n_ref1)) for cd in out),
                                       "".join("PBI"[cd.slice_type] for cd in out[:1]) + ":%d" % len(todo)))
         self.n_sweeps += 1
-        if self.nr:                                        # x264_noise_reduction_update at the end of every frame (encoder.c:1755)
-            c.check(L.x264hip_noise_reduction_update(c.h, C.byref(self.nr), o["noise_reduction"]), "noise_reduction_update")
-        # x264_fdec_filter_row for the kept frames: loop filter, borders, half-pel planes, on the elements that were just written
-        for pic_i, chains in filt.items():
-            recon, s = self.pool[pic_i], self.states[pic_i].st
-            el = self.elems_dev[pic_i]
-            lst = np.zeros(c.batch, np.int32)
-            lst[:len(chains)] = chains
-            el.set(lst)
-            c.check(L.x264hip_frame_ctx_elements(c.h, el.p, len(chains)), "frame_ctx_elements")
-            if o["deblock"]:
-                dp = DeblockParams(mb_type=s.mb_type, qp=s.qp, nnz=s.nnz, transform8x8=s.t8, mv=s.mv, ref=s.ref,
-                                   alpha_c0_offset=o["alpha_c0"], beta_offset=o["beta"], chroma_qp_offset=o["chroma_qp_offset"], state_layout=1,
-                                   sub8x8=1 if o["inter"] & 0x20 else 0)
-                c.check(L.x264hip_deblock_frame(c.h, C.byref(recon), C.byref(dp)), "deblock_frame")
-            c.check(L.x264hip_expand_border(c.h, C.byref(recon), 0), "expand_border")
-            c.check(L.x264hip_hpel_filter_frame(c.h, C.byref(recon)), "hpel_filter_frame")
-        c.check(L.x264hip_frame_ctx_elements(c.h, None, 0), "frame_ctx_elements")
         if self.post_scenecut:
             self._post = []
             for pic_i, chains in filt.items():
@@ -283,16 +242,61 @@ class StreamEncoder(ChainEncoder):
         self._keep = keep
         if not self.post_scenecut:
             self.lb.end([ci for ci, _ in todo])
-        self.last_bufs, self.last_ctx = rb, c
+        self.last_bufs, self.last_ctx = self.rd_bufs, c
         self._coding = {cd.frame for cd in out}
         return out
+
+    def _publish_elements(self, pic_i, chains):
+        """The element list of pool picture pic_i for x264hip_frame_ctx_elements: uploaded to the picture's own device array."""
+        el = self.elems_dev[pic_i]
+        lst = np.zeros(self.ctx.batch, np.int32)
+        lst[:len(chains)] = chains
+        el.set(lst)
+        return el.p
+
+    def _launch(self, c, pairs, tab_host, tab_dev, publish, ready, done_events=None):
+        """One chain-table launch on context c for the (chain, x264hip_look_frame) pairs, then x264_fdec_filter_row for the kept frames on the
+        elements that were just written.  tab_host / tab_dev: the launch's table buffers; publish(pool picture, chains): the address of
+        that picture's element list, the chains in it; ready(): called once the entries are built, before anything is enqueued -- whatever
+        the launch reads or overwrites is free after it; done_events: (I / P kernel, B kernel) completion events, or None.
+        Returns (out, keep, filt, ev): the Coded records, what the C calls read and must outlive them, {pool picture: chains that kept it},
+        the two timing events around the launch if self.sweep_events collects them."""
+        L = self.lib
+        keep, written, filt, out = [], set(), {}, []
+        entries = (ChainSweep * len(pairs))()
+        for k, (ci, fr) in enumerate(pairs):
+            entries[k], cd, pic_i = self._entry(ci, fr, keep)
+            written.add(pic_i)
+            out.append(cd)
+            if cd.slice_type != SLICE_B:                   # kept: filtered below
+                filt.setdefault(pic_i, []).append(ci)
+        ready()
+        for pic_i in written:
+            c.check(L.x264hip_mb_state_clear_progress(c.h, C.byref(self.states[pic_i].st)), "mb_state_clear_progress")
+        ev = None
+        if self.sweep_events is not None:
+            ev = (L.x264hip_event_create(), L.x264hip_event_create())
+            L.x264hip_event_record(C.c_void_p(ev[0]), C.c_void_p(c.stream))
+        if done_events:
+            c.check(L.x264hip_slice_sweep_chains_events(c.h, entries, len(pairs), tab_host, tab_dev, C.c_void_p(done_events[0]),
+                                                        C.c_void_p(done_events[1])), "slice_sweep_chains_events")
+        else:
+            c.check(L.x264hip_slice_sweep_chains(c.h, entries, len(pairs), tab_host, tab_dev), "slice_sweep_chains")
+        if ev:
+            L.x264hip_event_record(C.c_void_p(ev[1]), C.c_void_p(c.stream))
+        if self.nr:                                        # x264_noise_reduction_update at the end of every frame (encoder.c:1755)
+            c.check(L.x264hip_noise_reduction_update(c.h, C.byref(self.nr), self.opt["noise_reduction"]), "noise_reduction_update")
+        for pic_i, chains in filt.items():
+            c.check(L.x264hip_frame_ctx_elements(c.h, publish(pic_i, chains), len(chains)), "frame_ctx_elements")
+            self.filter_kept(c, self.pool[pic_i], self.states[pic_i].st)
+        c.check(L.x264hip_frame_ctx_elements(c.h, None, 0), "frame_ctx_elements")
+        return out, keep, filt, ev
 
     def _scenecut_hits(self):
         """After sync(): the chains whose P picture of the last sweep the reference would give up (encoder.c:1603-1644)."""
         if not self._post:
             return []
         L, d, lp = self.lib, self.ctx.dims, self.la_params
-        L.x264hip_scenecut_post.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]
         got, hits = {}, []
         for pic_i, ci, frame, gop in self._post:
             if pic_i not in got:
@@ -314,18 +318,17 @@ class StreamEncoder(ChainEncoder):
     def _entry(self, ci, fr, keep):
         """One chain's sweep for the frame its queue handed it: the x264hip_chain_sweep record (whatever it points at goes into `keep`), the
         chain's DPB bookkeeping (x264_reference_build_list before, x264_reference_update after), the Coded record, the pool picture written."""
-        o, ro, b, rb = self.opt, self.rd_opt, self.cqm.bufs, self._bufs_of(ci)
+        rb = self._bufs_of(ci)
         idr = fr.type == LA.TYPE_IDR
         stype = SLICE_I if fr.type in (LA.TYPE_IDR, LA.TYPE_I) else SLICE_B if fr.type == LA.TYPE_B else SLICE_P
         if idr:
             self.crefs[ci], self.c_last_idr[ci] = [], fr.frame
         refs_all = self.crefs[ci]
         poc = fr.poc
-        used = {r[0] for r in refs_all}
+        used = {r[3] for r in refs_all}
         pic_i = next(i for i in range(len(self.pool)) if i not in used)
         recon, state = self.pool[pic_i], self.states[pic_i]
-        refs = sorted([r for r in refs_all if r[1] < poc], key=lambda r: -r[1])[:o["n_refs"]] if stype != SLICE_I else []
-        refs1 = sorted([r for r in refs_all if r[1] > poc], key=lambda r: r[1])[:1] if stype == SLICE_B else []
+        refs, refs1 = self.ref_lists(refs_all, poc, stype)
         qp = fr.qp
         slot = self.look.slot(fr.frame)
         assert self.look.frame_of_slot[slot] == fr.frame, "input frame %d left its lookahead slot before it was coded (n_slots too small)" % fr.frame
@@ -335,19 +338,9 @@ class StreamEncoder(ChainEncoder):
             lw0 = self.look.mv_ptr(ci, fr.frame, 0, fr.frame - fr.ref0_frame) - 4 * n * ci
         if stype == SLICE_B and fr.lowres_l1:
             lw1 = self.look.mv_ptr(ci, fr.frame, 1, fr.ref1_frame - fr.frame) - 4 * n * ci
-        p = SliceParams(slice_type=stype, qp=qp, chroma_qp_offset=o["chroma_qp_offset"], me_method=o["me_method"], me_range=o["me_range"],
-                        subme=o["subme"], chroma_me=o["chroma_me"], mv_range=o["mv_range"] or 512, fast_pskip=o["fast_pskip"], dct_decimate=o["dct_decimate"],
-                        cabac=o["cabac"], transform8x8=o["transform8x8"], analyse_inter=o["inter"], analyse_intra=o["intra"],
-                        quant4_mf=b["quant4_mf"].ptr, quant4_bias=b["quant4_bias"].ptr, quant8_mf=b["quant8_mf"].ptr,
-                        quant8_bias=b["quant8_bias"].ptr, dequant4_mf=b["dequant4_mf"].ptr, dequant8_mf=b["dequant8_mf"].ptr,
-                        cost_mv=rb["cost_mv_all"].ptr + qp * (2 * COST_SPAN + 1) * 2, cost_mv_range=COST_SPAN, poc=poc, mixed_refs=o["mixed_refs"],      # (a row of the table of all QPs: no allocation while kernels run -- hipMalloc waits for the device)
-                        noise_reduction=o["noise_reduction"], nr=C.addressof(self.nr) if self.nr else None, lossless=self.lossless,
-                        lowres_mv=lw0)
-        rd = SliceRd(trellis=ro["trellis"], psy_rd=self.psy_rd_fix, write=1, cabac_init_idc=ro["cabac_init_idc"], i_frame=self.c_coded[ci],
-                     qp_min=ro["qp_min"], qp_max=ro["qp_max"], f_qpm=fr.f_qpm, aq_offset=self.aq_slots[slot][1].ptr if self.aq_slots else None,
-                     cost_mv_all=rb["cost_mv_all"].ptr, unquant4_mf=rb["unquant4_mf"].ptr, unquant8_mf=rb["unquant8_mf"].ptr,
-                     payload=rb["payload"].ptr, payload_cap=self.payload_cap, payload_len=rb["payload_len"].ptr, mb_bits=rb["mb_bits"].ptr,
-                     stale=rb["stale"].ptr, i_frame_stride=0)
+        # (cost_mv: a row of the table of all QPs: no allocation while kernels run -- hipMalloc waits for the device)
+        p = self.slice_params(stype, qp, poc, rb["cost_mv_all"].ptr + qp * (2 * COST_SPAN + 1) * 2, lw0)
+        rd = self.slice_rd(rb, fr.f_qpm, self.c_coded[ci], self.aq_slots[slot][1].ptr if self.aq_slots else None, 1, 0)
         p.rd = C.addressof(rd)
         keep += [p, rd]
         dsp = self.bopt["direct_spatial"]
@@ -355,18 +348,18 @@ class StreamEncoder(ChainEncoder):
             if self.direct_auto:                       # x264_slice_header_init, encoder.c:113-118
                 dsp = int(self.c_dscore[ci][1] > self.c_dscore[ci][0])
                 self._dscore_pending.append(ci)
-            sb = SliceB(fref1=C.addressof(self.pool[refs1[0][0]]), l1_state=C.addressof(refs1[0][2]), ref1_poc=refs1[0][1],
+            sb = SliceB(fref1=C.addressof(refs1[0][0]), l1_state=C.addressof(refs1[0][1]), ref1_poc=refs1[0][2],
                         weightb=self.bopt["weightb"], direct_spatial=dsp, lowres_mv1=lw1,
                         direct_score=self.dscore_dev.ptr if self.direct_auto else None)
             p.b = C.addressof(sb)
             keep.append(sb)
         for i, r in enumerate(refs):
-            p.ref_poc[i] = r[1]
-        arr = (C.c_void_p * max(len(refs), 1))(*[C.addressof(self.pool[r[0]]) for r in refs]) if refs else None
+            p.ref_poc[i] = r[2]
+        arr = (C.c_void_p * max(len(refs), 1))(*[C.addressof(r[0]) for r in refs]) if refs else None
         mine = MbState.from_buffer_copy(state.st)        # this chain's view of the state: the device arrays + its own frame-level scalars
         keep += [arr, mine]
         entry = ChainSweep(ci, C.addressof(self.look.pics[slot]), C.cast(arr, C.c_void_p) if arr else None, len(refs), C.addressof(recon),
-                                C.addressof(p), C.addressof(refs[0][2]) if refs else None, C.addressof(mine))
+                                C.addressof(p), C.addressof(refs[0][1]) if refs else None, C.addressof(mine))
         cd = Coded()
         cd.chain, cd.frame, cd.type, cd.slice_type, cd.qp, cd.f_qpm, cd.poc = ci, fr.frame, fr.type, stype, qp, fr.f_qpm, poc
         cd.n_ref0, cd.n_ref1, cd.i_satd = len(refs), len(refs1), fr.i_satd
@@ -375,7 +368,7 @@ class StreamEncoder(ChainEncoder):
         self._undo[ci] = (list(refs_all), self.c_coded[ci])
         self.coded_now[ci] = cd
         if stype != SLICE_B:                           # kept: filtered below, then this chain's newest reference
-            self.crefs[ci] = ([(pic_i, poc, mine)] + refs_all)[:self.dpb]
+            self.crefs[ci] = ([(recon, mine, poc, pic_i)] + refs_all)[:self.dpb]
         self.c_coded[ci] += 1
         return entry, cd, pic_i
 
@@ -388,7 +381,6 @@ class StreamEncoder(ChainEncoder):
         if self.aq_slots:
             c, L, ro = self.src_ctx, self.lib, self.rd_opt
             en, off = self.aq_slots[self.look.slot(frame)]
-            L.x264hip_adaptive_quant_frame.argtypes = [C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p]
             c.check(L.x264hip_adaptive_quant_frame(c.h, C.byref(pic), C.c_float(ro["aq_strength"]), en.p, off.p), "adaptive_quant_frame")
 
     def payloads(self):
@@ -442,8 +434,6 @@ class AsyncStreamEncoder(StreamEncoder):
             raise ValueError("AsyncStreamEncoder: n_frames (pictures per chain) is needed")
         if kw.get("noise_reduction"):
             raise ValueError("AsyncStreamEncoder: --nr updates its tables once per frame for all chains together: lock-step only")
-        if kw.get("direct_pred", 1) == 2:
-            pass                                         # temporal direct: x264hip_slice_rd.stale is per chain, frames of a chain stay in order
         bf = kw.get("bframes", 0)
         b_adapt = kw.get("b_adapt", 1)
         delay = (max(bf, 3) * 4 if b_adapt == 2 and bf else bf)
@@ -452,8 +442,6 @@ class AsyncStreamEncoder(StreamEncoder):
         from .frame import FrameCtx
         self.total, self.delay, self.drift = n_frames, delay, drift
         B = batch
-        lib.x264hip_host_alloc.restype = C.c_void_p
-        lib.x264hip_event_create.restype = C.c_void_p
         tb = lib.x264hip_chain_sweep_bytes()
         self.lctx = []
         for _ in range(launches):
@@ -475,6 +463,9 @@ class AsyncStreamEncoder(StreamEncoder):
         self.prepared = 0                                # pictures prepared on the device (for all chains)
         self.n_launches = 0
         self.launch_sizes = []
+        self.pic_events = {}                             # per picture number: what says "in place" to the sweeps that read it (_prepare_picture)
+        self.coded_all = [[] for _ in range(B)]          # per chain: the Coded records of its frames, in coding order
+        self.next_frame, self.cost_batches, self.undecided = {}, [], set()
         if self.post_scenecut:
             raise ValueError("AsyncStreamEncoder: the post-encode scene cut's check is made per step (StreamEncoder); run with pre_scenecut=1")
         if self.direct_auto:
@@ -517,8 +508,6 @@ class AsyncStreamEncoder(StreamEncoder):
         self._fill(fill, pic, f)
         self.look.prepare(f)
         # what says "picture f is in place" to the sweeps that will read it (they run on other streams)
-        if not hasattr(self, "pic_events"):
-            self.pic_events = {}
         ev = self.pic_events.pop(f - self.n_slots, None) or self.lib.x264hip_event_create()
         self.lib.x264hip_event_record(C.c_void_p(ev), C.c_void_p(self.src_ctx.stream))
         self.pic_events[f] = ev
@@ -571,10 +560,6 @@ class AsyncStreamEncoder(StreamEncoder):
         import time
         L, B = self.lib, self.ctx.batch
         target = self.total if until is None else min(until, self.total)
-        if not hasattr(self, "coded_all"):
-            self.coded_all = [[] for _ in range(B)]
-            self.next_frame, self.cost_batches, self.undecided = {}, [], set()
-            self.pic_events = {}
         idle = {ci for ci in range(B) if self.inflight_frame[ci] < 0}           # chains whose previous frame (if any) is done
         done = sum(1 for ci in range(B) if self.ncoded[ci] >= target)
         self._oldest = self._oldest_needed()
@@ -631,51 +616,28 @@ class AsyncStreamEncoder(StreamEncoder):
                 continue
             lc = free[0]
             c = lc["ctx"]
-            keep, written, filt, out = [], set(), {}, []
-            entries = (ChainSweep * len(go))()
-            frames_read = set()
-            for k, ci in enumerate(sorted(go)):
-                fr = self.next_frame.pop(ci)
-                entries[k], cd, pic_i = self._entry(ci, fr, keep)
-                written.add(pic_i)
-                out.append(cd)
-                if cd.slice_type != SLICE_B:
-                    filt.setdefault(pic_i, []).append(ci)
+            pairs = [(ci, self.next_frame.pop(ci)) for ci in sorted(go)]
+            for ci, fr in pairs:
                 self.inflight_frame[ci] = fr.frame
-                self.coded_all[ci].append(cd)
                 idle.discard(ci)
-                frames_read.add(fr.frame)
-            # the pictures these sweeps read were prepared on the lookahead's stream: wait (on the device) for the ones that may not be finished
-            for f in frames_read:
-                ev = self.pic_events.get(f)
-                if ev is not None and L.x264hip_event_query(C.c_void_p(ev)) != 1:
-                    L.x264hip_stream_wait_event(C.c_void_p(c.stream), C.c_void_p(ev))
-            for pic_i in written:
-                c.check(L.x264hip_mb_state_clear_progress(c.h, C.byref(self.states[pic_i].st)), "mb_state_clear_progress")
-            for pic_i, chains in filt.items():
+
+            def publish(pic_i, chains):                  # the launch's own list for that picture, in pinned host memory
                 np.ctypeslib.as_array(C.cast(lc["elems"][pic_i], C.POINTER(C.c_int32)), (B,))[:len(chains)] = chains
-            ev = None
-            if self.sweep_events is not None:
-                ev = (L.x264hip_event_create(), L.x264hip_event_create())
-                L.x264hip_event_record(C.c_void_p(ev[0]), C.c_void_p(c.stream))
-            c.check(L.x264hip_slice_sweep_chains_events(c.h, entries, len(go), C.c_void_p(lc["tab_host"]), lc["tab_dev"].p, C.c_void_p(lc["ev_ip"]),
-                                                        C.c_void_p(lc["ev_b"])), "slice_sweep_chains_events")
+                return C.c_void_p(lc["elems"][pic_i])
+
+            def wait_pictures():
+                # the pictures these sweeps read were prepared on the lookahead's stream: wait (on the device) for the ones that may not be finished
+                for f in {fr.frame for _, fr in pairs}:
+                    ev = self.pic_events.get(f)
+                    if ev is not None and L.x264hip_event_query(C.c_void_p(ev)) != 1:
+                        L.x264hip_stream_wait_event(C.c_void_p(c.stream), C.c_void_p(ev))
+
+            out, keep, filt, ev = self._launch(c, pairs, C.c_void_p(lc["tab_host"]), lc["tab_dev"].p, publish, wait_pictures, (lc["ev_ip"], lc["ev_b"]))
+            for cd in out:
+                self.coded_all[cd.chain].append(cd)
             if ev:
-                L.x264hip_event_record(C.c_void_p(ev[1]), C.c_void_p(c.stream))
                 px = self.ctx.dims.mb_w * 16 * self.ctx.dims.lines_y
                 self.sweep_events.append((ev[0], ev[1], sum(1 for cd in out if cd.slice_type != SLICE_B), sum(px * (3.0 + 4.5 * (cd.n_ref0 + cd.n_ref1)) for cd in out if cd.slice_type != SLICE_B), "IP"))
-            o = self.opt
-            for pic_i, chains in filt.items():
-                recon, s_ = self.pool[pic_i], self.states[pic_i].st
-                c.check(L.x264hip_frame_ctx_elements(c.h, C.c_void_p(lc["elems"][pic_i]), len(chains)), "frame_ctx_elements")
-                if o["deblock"]:
-                    dp = DeblockParams(mb_type=s_.mb_type, qp=s_.qp, nnz=s_.nnz, transform8x8=s_.t8, mv=s_.mv, ref=s_.ref,
-                                       alpha_c0_offset=o["alpha_c0"], beta_offset=o["beta"], chroma_qp_offset=o["chroma_qp_offset"], state_layout=1,
-                                       sub8x8=1 if o["inter"] & 0x20 else 0)
-                    c.check(L.x264hip_deblock_frame(c.h, C.byref(recon), C.byref(dp)), "deblock_frame")
-                c.check(L.x264hip_expand_border(c.h, C.byref(recon), 0), "expand_border")
-                c.check(L.x264hip_hpel_filter_frame(c.h, C.byref(recon)), "hpel_filter_frame")
-            c.check(L.x264hip_frame_ctx_elements(c.h, None, 0), "frame_ctx_elements")
             self.last_ctx = c
             if on_launch is not None:
                 on_launch(out, c, lc["ev_b"])            # e.g. copies of the payloads just produced (a B chain's: behind ev_b)
