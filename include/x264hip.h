@@ -158,6 +158,8 @@ int x264hip_lowres_init_frame(x264hip_frame_ctx *c, x264hip_picture *pic);
  * four 8x8c predictors and the six directional 8x8 predictors on the filtered edge, scored with
  * SATD 8x8; out[mb] = min + 5 = frame->i_intra_cost[mb].                                      */
 int x264hip_lookahead_intra_frame(x264hip_frame_ctx *c, const x264hip_picture *pic, int32_t *out_cost_dev);
+/* The same scored with SAD 8x8: h->pixf.mbcmp when lossless (R/encoder/encoder.c:610).  Goes with x264hip_look_params.lossless = 1. */
+int x264hip_lookahead_intra_frame_sad(x264hip_frame_ctx *c, const x264hip_picture *pic, int32_t *out_cost_dev);
 /* AQ energy: pixf.var of Y 16x16 and U,V 8x8 per macroblock
  * (x264_adaptive_quant_frame's ac_energy_mb, R/encoder/ratecontrol.c:171-195).
  * out[mb] = var16(Y) + var8(U) + var8(V)                                    */
@@ -341,8 +343,16 @@ typedef struct {
     int noise_reduction;
     const struct x264hip_nr_state *nr;
     /* h->mb.b_lossless (constant QP 0, R/encoder/encoder.c:401-421): predictive lossless intra prediction, the prediction error
-     * itself in zigzag order as levels, SAD for every comparison, no transform-size analysis.  The caller applies the rest of
-     * x264_validate_parameters: qp 0 for every slice, chroma_qp_offset 0, fast_pskip 0, noise_reduction 0, 8x8dct only with CABAC */
+     * itself in zigzag order as levels, SAD for every comparison (mbcmp at every subme), no SATD transform-size analysis.  Built in both
+     * variants of the sweep for I and P slices: the wavefront schedule (rd = NULL) and the raster-order variant with the CABAC writer in
+     * the loop, subme 0..9 -- there the RD levels price trial encodes whose reconstruction is the source (distortion 0: the bits decide),
+     * x264_mb_analyse_transform_rd may turn the 8x8 transform on for inter macroblocks, I_PCM stays a candidate, and the RD refinement
+     * of subme 8-9 predicts and codes its trials losslessly too.  The caller applies the rest of x264_validate_parameters, and a call
+     * that has not is refused: qp 0 for every slice, chroma_qp_offset 0, fast_pskip 0, noise_reduction 0, 8x8dct only with CABAC, and in
+     * the raster variant rd.trellis 0, rd.psy_rd 0, rd.aq_offset NULL.  B slices with lossless are refused (the reference turns B
+     * frames off); a chain table (x264hip_slice_sweep_chains) is all-lossless or not at all.  Payload space: one macroblock's worst case
+     * stays inside the 8192 bytes the sweep keeps free, but below the RD levels (no I_PCM candidate) provide 6144 bytes per macroblock
+     * instead of the lossy 800 if hostile content must never abort a frame (csrc/slice_kernel.h: SW_MB_BYTES_MAX) */
     int lossless;
     const struct x264hip_slice_rd *rd;   /* NULL: the wavefront schedule of round 1; set: the raster-order variant (below) */
     /* fenc->lowres_mvs[0][fenc->i_frame - fref0[0]->i_frame - 1] of every chain (h->frames.b_have_lowres): device [batch][n_mb][2]
@@ -554,7 +564,9 @@ int x264hip_lookahead_oldest_live(const x264hip_lookahead *la);
  * out_dev[task] = {i_cost_est, i_intra_mbs, i_cost_est[0][0], 0}.  Two tasks of one call must not search the same (chain, frame, list,
  * distance), and a bidirectional task needs frames[p1]'s list-0 vectors over d0 + d1 from an EARLIER call (x264hip_lookahead_get asks
  * in that order).  Asynchronous on the context's stream; staging_host (pinned) and tasks_dev hold n_tasks * x264hip_lookahead_task_bytes()
- * and must not be reused before the stream has passed the call.  Refused: frames of <= 2 macroblock rows / columns, subme < 2, lossless. */
+ * and must not be reused before the stream has passed the call.  lossless = 1: every comparison is SAD (the search's sub-pel refinement,
+ * the bidirectional tries), and the intra costs must come from x264hip_lookahead_intra_frame_sad.  Refused: frames of <= 2 macroblock
+ * rows / columns, and subme < 2 without lossless (SAD there too, not built). */
 typedef struct {
     const x264hip_picture *pic;
     const int32_t *intra_cost;   /* device [batch][n_mb] */

@@ -14,6 +14,10 @@ void x264hip_launch_slice_rf(const SwArgs &a, const SwRefs &t, const SwRd &r, hi
 void x264hip_launch_slice_rd_ch(const SwDesc *tab, int n, hipStream_t stream);
 void x264hip_launch_slice_bt_ch(const SwDesc *tab, int n, hipStream_t stream);
 void x264hip_launch_slice_rf_ch(const SwDesc *tab, int n, hipStream_t stream);
+void x264hip_launch_slice_ll(const SwArgs &a, const SwRefs &t, const SwRd &r, hipStream_t stream);
+void x264hip_launch_slice_ll_rf(const SwArgs &a, const SwRefs &t, const SwRd &r, hipStream_t stream);
+void x264hip_launch_slice_ll_ch(const SwDesc *tab, int n, hipStream_t stream);
+void x264hip_launch_slice_ll_rf_ch(const SwDesc *tab, int n, hipStream_t stream);
 
 // b_fast_intra's raster-order term, settled once the frame is complete: macroblocks whose analysis went on without
 // knowing it (it could not change their type) recorded the statistics term for the other answer in cost_alt.
@@ -129,7 +133,7 @@ extern "C" int x264hip_noise_reduction_update(x264hip_frame_ctx *c, const x264hi
 
 struct ChainAux { hipStream_t stream = nullptr; hipEvent_t ready = nullptr, done = nullptr; };
 // The three argument structures of one sweep launch from the ABI's description of it, and which kernel codes it
-enum { SW_KIND_PLAIN = 0, SW_KIND_RD, SW_KIND_RF, SW_KIND_B, SW_KIND_BT };
+enum { SW_KIND_PLAIN = 0, SW_KIND_RD, SW_KIND_RF, SW_KIND_B, SW_KIND_BT, SW_KIND_LL, SW_KIND_LL_RF, SW_N_KINDS };      // LL: the lossless raster kernels (frame_slice_ll*.hip)
 static void sweep_note_frame(const x264hip_slice_params *p, int n_refs, x264hip_mb_state *out);
 static int sweep_build(x264hip_frame_ctx *c, const x264hip_picture *fenc, const x264hip_picture *const *refs, int n_refs,
                        x264hip_picture *recon, const x264hip_slice_params *p, const x264hip_mb_state *l0,
@@ -162,7 +166,12 @@ static int sweep_build(x264hip_frame_ctx *c, const x264hip_picture *fenc, const 
         if (prd->trellis && (!prd->write || !prd->unquant4_mf || (p->transform8x8 && !prd->unquant8_mf))) { set_error("slice_sweep: trellis needs write = 1 and the unquant tables"); return -1; }
         if (prd->trellis < 0 || prd->trellis > 2) { set_error("slice_sweep: trellis %d", prd->trellis); return -1; }
         if (prd->aq_offset && !prd->cost_mv_all) { set_error("slice_sweep: adaptive quantisation needs cost_mv_all"); return -1; }
-        if (p->lossless) { set_error("slice_sweep: lossless is not built in the raster variant"); return -1; }
+        // lossless in the raster variant: what x264_validate_parameters turns off (R/encoder/encoder.c:401-429, ratecontrol.c CQP: no AQ) is the
+        // caller's precondition, as for the wavefront variant below; B slices are refused above (the reference turns B frames off)
+        if (p->lossless && prd->trellis) { set_error("slice_sweep: lossless with trellis (x264_validate_parameters turns trellis off at QP 0)"); return -1; }
+        if (p->lossless && prd->psy_rd) { set_error("slice_sweep: lossless with psy-rd (x264_validate_parameters turns psy-rd off at QP 0)"); return -1; }
+        if (p->lossless && p->chroma_qp_offset) { set_error("slice_sweep: lossless with a chroma QP offset (x264_validate_parameters clears chroma_qp_offset at QP 0)"); return -1; }
+        if (p->lossless && prd->aq_offset) { set_error("slice_sweep: lossless with adaptive quantisation (constant QP 0 has no AQ: every macroblock is coded at QP 0)"); return -1; }
         if (mbrd && (p->analyse_inter & 0x20)) { set_error("slice_sweep: sub-8x8 partitions with the RD levels not built (their partial bit counts read cache entries the previous macroblock left)"); return -1; }
         if (!out->mvd) { set_error("slice_sweep: mb_state without mvd"); return -1; }
     }
@@ -271,7 +280,9 @@ static int sweep_build(x264hip_frame_ctx *c, const x264hip_picture *fenc, const 
             r.col_type = (const signed char *)pb->l1_state->mb_type; r.col_ref = (const signed char *)pb->l1_state->ref; r.col_mv = pb->l1_state->mv;
             // the extended B kernel (temporal direct prediction, the lookahead's candidates) only where it is needed: the plain one is 6-8 % faster
             kind = r.direct_temporal || r.direct_score || a.lowres0 || a.lowres1 ? SW_KIND_BT : SW_KIND_B;
-        } else
+        } else if (a.lossless)
+            kind = mbrd >= 2 ? SW_KIND_LL_RF : SW_KIND_LL;  // kernels of their own (k_lossless_raster)
+        else
             kind = mbrd >= 2 ? SW_KIND_RF : SW_KIND_RD;     // subme 8-9: the I / P kernel with the RD refinement (slice_refine.h)
     }
     return 0;
@@ -309,6 +320,8 @@ extern "C" int x264hip_slice_sweep_frame(x264hip_frame_ctx *c, const x264hip_pic
     case SW_KIND_B: x264hip_launch_slice_b(a, t, r, c->stream); break;
     case SW_KIND_RF: x264hip_launch_slice_rf(a, t, r, c->stream); break;
     case SW_KIND_RD: x264hip_launch_slice_rd(a, t, r, c->stream); break;
+    case SW_KIND_LL: x264hip_launch_slice_ll(a, t, r, c->stream); break;
+    case SW_KIND_LL_RF: x264hip_launch_slice_ll_rf(a, t, r, c->stream); break;
     default: {
         const dim3 grid((unsigned)(a.batch_pad * a.mb_h)), block(64);
         switch (a.lossless ? 0 : wpe) {
@@ -362,8 +375,8 @@ static int sweep_chains(x264hip_frame_ctx *c, x264hip_chain_sweep *e, int n, voi
     if (n <= 0) return 0;
     if (!staging_host || !table_dev) { set_error("slice_sweep_chains: staging / table buffers missing"); return -1; }
     SwDesc *st = (SwDesc *)staging_host;
-    // entries sorted by kernel: [RD | RF | BT]; a first pass builds, a second places
-    int cnt[5] = {0, 0, 0, 0, 0};
+    // entries sorted by kernel: [RD | RF | BT], or [LL | LL_RF] when the launch is lossless; a first pass builds, a second places
+    int cnt[SW_N_KINDS] = {0};
     static thread_local std::vector<SwDesc> tmp;
     static thread_local std::vector<int> kinds;
     tmp.resize((size_t)n); kinds.resize((size_t)n);
@@ -378,9 +391,14 @@ static int sweep_chains(x264hip_frame_ctx *c, x264hip_chain_sweep *e, int n, voi
         kinds[i] = kind; cnt[kind]++;
         sweep_note_frame(s.params, s.n_refs, s.out);
     }
-    int base[5], at[5];
+    // one launch is all-lossless or not at all: QP 0 changes what every table and buffer of a chain means (SPS profile, payload bound,
+    // SAD lookahead), so a table that mixes the two is a caller's mistake, not a schedule
+    const int n_ll = cnt[SW_KIND_LL] + cnt[SW_KIND_LL_RF];
+    if (n_ll && n_ll != n) { set_error("slice_sweep_chains: %d of %d entries are lossless (QP 0): a chain table is all-lossless or not at all", n_ll, n); return -1; }
+    int base[SW_N_KINDS] = {0}, at[SW_N_KINDS];
     base[SW_KIND_RD] = 0; base[SW_KIND_RF] = cnt[SW_KIND_RD]; base[SW_KIND_BT] = base[SW_KIND_RF] + cnt[SW_KIND_RF];
-    for (int k = 0; k < 5; k++) at[k] = base[k];
+    base[SW_KIND_LL] = 0; base[SW_KIND_LL_RF] = cnt[SW_KIND_LL];
+    for (int k = 0; k < SW_N_KINDS; k++) at[k] = base[k];
     for (int i = 0; i < n; i++) st[at[kinds[i]]++] = tmp[i];
     HIPCHK(hipMemcpyAsync(table_dev, st, sizeof(SwDesc) * (size_t)n, hipMemcpyHostToDevice, c->stream));
     const SwDesc *tab = (const SwDesc *)table_dev;
@@ -402,6 +420,8 @@ static int sweep_chains(x264hip_frame_ctx *c, x264hip_chain_sweep *e, int n, voi
     // the I / P kernel first: its wavefronts -- the step's long ones -- are dealt evenly over the SIMDs before the B kernel's fill the rest
     if (cnt[SW_KIND_RD]) x264hip_launch_slice_rd_ch(tab + base[SW_KIND_RD], cnt[SW_KIND_RD], c->stream);
     if (cnt[SW_KIND_RF]) x264hip_launch_slice_rf_ch(tab + base[SW_KIND_RF], cnt[SW_KIND_RF], c->stream);
+    if (cnt[SW_KIND_LL]) x264hip_launch_slice_ll_ch(tab + base[SW_KIND_LL], cnt[SW_KIND_LL], c->stream);
+    if (cnt[SW_KIND_LL_RF]) x264hip_launch_slice_ll_rf_ch(tab + base[SW_KIND_LL_RF], cnt[SW_KIND_LL_RF], c->stream);
     if (cnt[SW_KIND_BT]) x264hip_launch_slice_bt_ch(tab + base[SW_KIND_BT], cnt[SW_KIND_BT], two ? ax->stream : c->stream);
     if (two && join) {
         HIPCHK(hipEventRecord(ax->done, ax->stream));

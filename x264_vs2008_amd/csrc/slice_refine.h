@@ -69,7 +69,7 @@
                             const int m = i < 0 ? predc : (int)((flist >> (4 * i)) & 15);
                             bool b_dct = false;
                             if (i >= 0) {
-                                sw_pred8c(s, m, lane, 0);
+                                sw_pred8c(s, m, lane, LL);                  // (lossless: x264_predict_lossless_8x8_chroma, analyse.c:930)
                                 b_dct = cbp_chroma != 0;             // "if we've already found a mode that needs no residual ..." (the LAST trial's cbp)
                             }
                             if (b_dct) cbp_chroma = sw_encode_chroma(s, a, Q, tq, 0, lane);
@@ -105,7 +105,8 @@
                     int best_mode = 0, best_nnz = 0;
                     for (int i = 0; i < n; i++) {
                         const int mode = (int)((list >> (4 * i)) & 15);
-                        if (lane < 16) dst[(lane >> 2) * FD + (lane & 3)] = s.pt4[(s.p4lut[mode * 4 + (lane >> 2)] >> (8 * (lane & 3))) & 255];
+                        if (lane < 16) dst[(lane >> 2) * FD + (lane & 3)] = LL && mode < 2 ? (u8)sw_ll_px(s, 0, mode, bx + (lane & 3), by + (lane >> 2))      // x264_predict_lossless_4x4, analyse.c:968
+                                                                             : s.pt4[(s.p4lut[mode * 4 + (lane >> 2)] >> (8 * (lane & 3))) & 255];
                         WAVE_SYNC();
                         sw_encode_i4x4(s, a, Q, tq, idx, cbp_luma, lane);
                         int d2 = 0, pix = 0;
@@ -148,7 +149,8 @@
                         const int mode = (int)((list >> (4 * i)) & 15);
                         if (UNI(sf.i8dir[mode][idx]) > thresh) continue;
                         {
-                            const int v = s.pt8[(s.p8lut[(mode * 8 + (lane >> 3)) * 2 + ((lane >> 2) & 1)] >> (8 * (lane & 3))) & 255];
+                            int v = s.pt8[(s.p8lut[(mode * 8 + (lane >> 3)) * 2 + ((lane >> 2) & 1)] >> (8 * (lane & 3))) & 255];
+                            if (LL && mode < 2) v = sw_ll_px(s, 0, mode, bx + (lane & 7), by + (lane >> 3));      // x264_predict_lossless_8x8, analyse.c:1024
                             WAVE_SYNC();
                             dst[(lane >> 3) * FD + (lane & 7)] = (u8)v;
                             WAVE_SYNC();
@@ -209,7 +211,7 @@
                     const int j = t + (lane >> 4);
                     const bool in = j < n;
                     const int x = q_omx + (in ? mx_nib(dxs, base + j) : 0), y = q_omy + (in ? mx_nib(dys, base + j) : 0);
-                    const int cost = subpel_sum16_lane(cu, x, y, 1, 0) + cu.lane_cost(x, y);
+                    const int cost = subpel_sum16_lane(cu, x, y, !LL, 0) + cu.lane_cost(x, y);      // mbcmp_unaligned: SAD when lossless
 #pragma unroll
                     for (int k = 0; k < 4; k++)
                         if (t + k < n) {
@@ -331,6 +333,26 @@
                     }
                     // ... its luma residual ...
                     int nnz8 = 0;
+                    if constexpr (LL) {
+                        // macroblock.c:928-958: zigzag sub_8x8 / sub_4x4 of the luma block, sub_4x4 of either chroma block with its first level
+                        // (the DC's place) cleared; the reconstruction is the source
+                        int c8 = 0;
+                        if (t8) sw_ll_i8x8(s, b8, c8, lane);
+                        else for (int i4 = 4 * b8; i4 < 4 * b8 + 4; i4++) sw_ll_i4x4(s, i4, c8, lane);
+                        nnz8 = c8 != 0;
+                        cbp_luma |= nnz8 << b8;
+                        {
+                            const int ch = (lane >> 4) & 1, p = lane & 15, c = SW_ZZ4(p), cblk = 4 * ch + b8;
+                            const int o_e = 256 + 64 * ch + ((y8 >> 1) + (c & 3)) * 8 + (x8 >> 1) + (c >> 2), o_d = (ch ? FDV : FDU) + ((y8 >> 1) + (c & 3)) * FD + (x8 >> 1) + (c >> 2);
+                            int v = lane < 32 ? (int)s.fe[o_e] - (int)s.fd[o_d] : 0;
+                            if (p == 0) v = 0;
+                            const unsigned long long m = __ballot(v != 0);
+                            if (lane < 32) { s.lv_cac[16 * cblk + p] = (i16)v; s.fd[o_d] = s.fe[o_e]; }
+                            if (lane == 0 || lane == 16) s.nnz[16 + cblk] = (u8)(((m >> lane) & 0xffffull) != 0);
+                            WAVE_SYNC();
+                        }
+                        continue;
+                    }
                     if (t8) {
                         sw_luma8x8_fwd(s, Q, tq, 1, 1 << b8, lane);
                         const int sc = UNI(s.score[b8]);

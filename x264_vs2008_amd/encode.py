@@ -3,6 +3,8 @@
     python -m x264_vs2008_amd.encode --crf 23 --ref 3 --bframes 3 --b-adapt 1 --subme 7 --8x8dct --trellis 1 --weightb --mixed-refs -o out.264 in.y4m
     python -m x264_vs2008_amd.encode --qp 26 --no-cabac --me dia --subme 0 --partitions none --no-deblock --scenecut -1 -o out.264 in.yuv 352x288
     python -m x264_vs2008_amd.encode [options] -o out_%d.264 a.y4m b.y4m c.y4m        # one stream per input, coded side by side (same size and options)
+    python -m x264_vs2008_amd.encode --qp 0 -o out.264 in.y4m                         # lossless (High 4:4:4 Predictive SPS): what x264_validate_parameters
+                                                                                      # turns off at QP 0 is off here too, the lookahead scores with SAD
 
 Option names and meanings are `x264 --longhelp`'s (R/x264.c:386-487, x264_param_parse R/common/common.c:206-587; tests/test_cpu_encode_cli.py
 parses the same argument lists with the reference's own x264_param_parse and compares x264_param2string).  The parameters go through

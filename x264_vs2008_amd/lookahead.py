@@ -203,7 +203,9 @@ class LookaheadDevice:
         """x264_frame_init_lowres + the intra half of the cost for every chain's copy of `frame` (encoder.c:1415-1418, slicetype.c:186-245)."""
         s, ctx, lib = self.slot(frame), self.ctx, self.lib
         ctx.check(lib.x264hip_lowres_init_frame(ctx.h, C.byref(self.pics[s])), "lowres_init_frame")
-        ctx.check(lib.x264hip_lookahead_intra_frame(ctx.h, C.byref(self.pics[s]), self.intra[s].p), "lookahead_intra_frame")
+        # (lossless: mbcmp is SAD, in the intra half as in the cost kernel)
+        intra = lib.x264hip_lookahead_intra_frame_sad if self.params.lossless else lib.x264hip_lookahead_intra_frame
+        ctx.check(intra(ctx.h, C.byref(self.pics[s]), self.intra[s].p), "lookahead_intra_frame")
 
     def run(self, tasks):
         """tasks: [(chain, b, p0, p1, do_search0, do_search1)] with input frame numbers.  Returns int32 [n][3]: score, intra_mbs, cost00."""

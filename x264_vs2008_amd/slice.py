@@ -52,6 +52,8 @@ class CavlcParams(C.Structure):
 
 PAYLOAD_LEAD = 64
 MB_BYTES_MAX = 8192          # SW_MB_BYTES_MAX (csrc/slice_kernel.h): the sweep stops before a macroblock whose worst case might not fit
+MB_BYTES_AVG = 800           # what the default payload buffer provides per macroblock
+LL_MB_BYTES = 6144           # ... for a lossless chain below the RD levels: no I_PCM candidate caps a macroblock there (derived beside SW_MB_BYTES_MAX)
 
 
 class SliceParams(C.Structure):
@@ -130,6 +132,12 @@ class ChainEncoder:
                  trellis=0, psy_rd=0.0, aq_mode=0, aq_strength=1.0, write=0, cabac_init_idc=0, qp_min=0, qp_max=51, payload_cap=0, raster=None,
                  bframes=0, weightb=0, direct_pred=1, lanes=0, levels=True):
         self.lib = lib
+        self.lossless = int(qp == 0)
+        if self.lossless:              # x264_validate_parameters, R/encoder/encoder.c:401-429: what constant QP 0 turns off (CQP: no adaptive quantisation)
+            fast_pskip, noise_reduction, chroma_qp_offset, trellis, psy_rd, aq_mode = 0, 0, 0, 0, 0.0, 0
+            transform8x8 = int(bool(transform8x8 and cabac))
+            if not transform8x8:
+                inter, intra = inter & ~2, intra & ~2
         # x264_validate_parameters (R/encoder/encoder.c:493-522): what the RD-side options do to each other
         trellis = min(max(trellis, 0), 2) if cabac else 0
         psy_rd = 0.0 if subme < 6 else min(max(float(psy_rd), 0.0), 10.0)
@@ -146,12 +154,6 @@ class ChainEncoder:
         self.raster = bool(subme >= 6 or trellis or aq_mode or (write and not self.cavlc)) if raster is None else bool(raster)
         self.rd_opt = dict(trellis=trellis, aq_mode=aq_mode, aq_strength=aq_strength, write=int(bool((write and not self.cavlc) or subme >= 6 or trellis)),
                            cabac_init_idc=cabac_init_idc, qp_min=qp_min, qp_max=qp_max)
-        self.lossless = int(qp == 0)
-        if self.lossless:              # x264_validate_parameters, R/encoder/encoder.c:401-421
-            fast_pskip, noise_reduction, chroma_qp_offset = 0, 0, 0
-            transform8x8 = int(bool(transform8x8 and cabac))
-            if not transform8x8:
-                inter, intra = inter & ~2, intra & ~2
         self.ctx = FrameCtx(lib, width, height, batch=batch)
         self.opt = dict(qp=qp, me_method=me_method, me_range=me_range, subme=subme, n_refs=n_refs, inter=inter, intra=intra,
                         transform8x8=transform8x8, fast_pskip=fast_pskip, dct_decimate=dct_decimate, chroma_me=chroma_me, cabac=cabac,
@@ -163,7 +165,7 @@ class ChainEncoder:
         if self.raster:
             d, B = self.ctx.dims, batch
             n = d.mb_w * d.mb_h
-            cap = payload_cap or (n * 800 + MB_BYTES_MAX + 128 + PAYLOAD_LEAD)
+            cap = payload_cap or (n * (LL_MB_BYTES if self.lossless and subme < 6 else MB_BYTES_AVG) + MB_BYTES_MAX + 128 + PAYLOAD_LEAD)
             rb = self._frame_bufs(B, n, cap, aq_mode)
             # p_cost_mv of every QP and the unquant tables, built by the library's host C (x264hip_cost_mv_table / _unquant_table)
             tabs = np.zeros((52, 2 * COST_SPAN + 1), np.int16)
@@ -191,7 +193,7 @@ class ChainEncoder:
         if self.cavlc and not self.raster:
             d = self.ctx.dims
             n = d.mb_w * d.mb_h
-            self.payload_cap = payload_cap or (n * 800 + MB_BYTES_MAX + 128 + PAYLOAD_LEAD)
+            self.payload_cap = payload_cap or (n * MB_BYTES_AVG + MB_BYTES_MAX + 128 + PAYLOAD_LEAD)
             self.rd_bufs = self._frame_bufs(batch, n, self.payload_cap, 0)
         self.i_frame, self.i_frame_stride = 0, 0      # shard.py sets both when the chains are the GOPs of one stream
         self._fenc = None              # the picture upload() fills: allocated on first use (a caller with its own source pictures never needs it)
@@ -346,7 +348,7 @@ class ChainEncoder:
                     L.x264hip_event_destroy(C.c_void_p(ev))
             self.b_readers = keep
         refs, refs1 = self.ref_lists(self.refs, poc, stype)
-        qp = iframe_qp(o["qp"]) if idr else bframe_qp(o["qp"]) if is_b else o["qp"]
+        qp = iframe_qp(o["qp"]) if idr else bframe_qp(o["qp"]) if is_b else o["qp"]      # (lossless: ip_factor = 1, and QP 0 stays 0 under the default's clamp)
         self.last_is_b, self.last_poc = is_b, poc
         p = self.slice_params(stype, qp, poc, self.cost_table(qp).ptr, lowres_mv.ptr if lowres_mv is not None else None)
         if self.raster:

@@ -50,6 +50,10 @@ class StreamEncoder(ChainEncoder):
         if not self.raster or not self.rd_opt["write"]:
             raise ValueError("StreamEncoder: the chain-table sweep is the raster variant with the entropy coder in the loop")
         o, d = self.opt, self.ctx.dims
+        if self.lossless:              # x264_validate_parameters (R/encoder/encoder.c:401-417): constant QP 0 for every frame type, no B frames
+            crf, ip_factor, pb_factor = None, 1.0, 1.0
+            if self.bopt["bframes"]:
+                raise ValueError("StreamEncoder: lossless (qp 0) has no B frames (x264_validate_parameters sets bframes = 0)")
         keyint = o["keyint"] if o["keyint"] > 0 else 1 << 30
         self.la_params = LA.make_params(d.mb_w, d.mb_h, bframes=self.bopt["bframes"], b_adapt=b_adapt if self.bopt["bframes"] else 0, bframe_bias=bframe_bias,
                                         keyint_max=keyint, keyint_min=keyint_min, scenecut_threshold=scenecut_threshold, pre_scenecut=pre_scenecut,
