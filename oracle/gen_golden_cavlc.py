@@ -1,6 +1,6 @@
 """TEST INFRASTRUCTURE -- regenerates tests/golden/cavlc_*.npz: the slice_data() bytes the REFERENCE's CAVLC writer
 (x264_macroblock_write_cavlc inside oracle/ref_slice.c's loop, refslice_encode_chain2 with cabac = 0) produces for the chains of
-tests/test_gpu_cavlc.py, and tests/golden/cavlc_batch_uf.npz: the clips of tests/test_gpu_full_batch.py's wavefront chains (bench.py --preset
+tests/test_gpu_cavlc.py (tests/cavlc_util.py), and tests/golden/cavlc_batch_uf.npz: the clips of tests/test_gpu_full_batch.py's wavefront chains (tests/full_batch_util.py; (bench.py --preset
 cif's flag set), written byte for byte the same on every run.  Needs oracle/_ref/libx264ref.so.
 
     python -m oracle.gen_golden_cavlc
@@ -16,7 +16,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 
 def main_batch():
-    import test_gpu_full_batch as T
+    import full_batch_util as T
     from oracle.gen_golden_stream import save_npz
     from oracle import refslice as rs
     c = T.LOCK_WAVE
@@ -30,7 +30,7 @@ def main_batch():
 
 def main():
     main_batch()
-    import test_gpu_cavlc as T
+    import cavlc_util as T
     for name in sorted(T.CONFIGS):
         _, pays, a = T.reference(T.CONFIGS[name])
         types = [int(np.bincount(a["mb_type"][f].astype(np.int64) & 31, minlength=8)[6]) for f in range(len(pays))]

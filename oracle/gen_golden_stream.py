@@ -1,7 +1,7 @@
 """TEST INFRASTRUCTURE -- regenerates tests/golden/stream_*.npz: the REFERENCE's whole encoder (frame queue, x264_slicetype_decide,
 x264_ratecontrol_start, the slice loop with the entropy coder; oracle/ref_slice.c refslice_encode_stream) on the clips and options of
-tests/test_gpu_stream.py -- per coded frame the input number, slice type, QP and the slice_data() bytes -- and
-tests/golden/stream_batch_{med,slow}.npz, the clips of tests/test_gpu_full_batch.py (bench.py's MED and SLOW flag sets) with each coded
+tests/test_gpu_stream.py (tests/stream_util.py) -- per coded frame the input number, slice type, QP and the slice_data() bytes -- and
+tests/golden/stream_batch_{med,slow}.npz, the clips of tests/test_gpu_full_batch.py (tests/full_batch_util.py; bench.py's MED and SLOW flag sets) with each coded
 frame's frame_num besides; those are written byte for byte the same on every run (save_npz).
 Needs oracle/_ref/libx264ref.so (`make -C oracle ref`, i.e. /root/reference).
 
@@ -33,7 +33,7 @@ def save_npz(path, arrays):
 
 
 def main_batch():
-    import test_gpu_full_batch as T
+    import full_batch_util as T
     for name in sorted(T.FLAGS):
         out = {}
         for i, a in enumerate(T.reference(name)):
@@ -47,7 +47,7 @@ def main_batch():
 def main():
     main_batch()
     import look_cases as K
-    import test_gpu_stream as T
+    import stream_util as T
     for name in sorted(T.CONFIGS):
         out = {}
         for i, c in enumerate(T.chains(name, T.SEEDS[name])):

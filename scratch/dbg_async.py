@@ -3,7 +3,7 @@ sys.path.insert(0, '/root/repo'); sys.path.insert(0, '/root/repo/tests')
 import numpy as np
 from x264_vs2008_amd import lib as L
 from x264_vs2008_amd.frame import cqm_init, FrameCtx, DeviceArray
-import look_cases as K, test_gpu_stream as T
+import look_cases as K, stream_util as T
 hip = L.load(0)
 def probe(tag):
     ctx = FrameCtx(hip, 128, 96, batch=1)

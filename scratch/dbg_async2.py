@@ -2,7 +2,7 @@ import sys, ctypes as C, traceback
 sys.path.insert(0, '/root/repo'); sys.path.insert(0, '/root/repo/tests')
 import numpy as np
 from x264_vs2008_amd import lib as L
-import look_cases as K, test_gpu_stream as T
+import look_cases as K, stream_util as T
 from x264_vs2008_amd import frame as F
 hip = L.load(0)
 orig = F.FrameCtx.upload

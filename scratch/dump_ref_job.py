@@ -4,10 +4,10 @@ import ctypes as C, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
 import numpy as np
-import look_cases as K, test_gpu_stream as T
+import look_cases as K, stream_util as T
 from oracle import refslice as rs
 if sys.argv[1] == "cavlc":                      # python scratch/dump_ref_job.py cavlc <name> <out>: tests/test_gpu_cavlc.py's live configuration (clip t0 = 37)
-    import test_gpu_cavlc as TC
+    import cavlc_util as TC
     c = TC.CONFIGS[sys.argv[2]]
     y, u, v = rs.clip(c["w"], c["h"], c["n"], 37)
     p, e = rs.make_params(c["w"], c["h"], c["n"], **c["kw"]), rs.make_ext(write=1, **c.get("ext", {}))

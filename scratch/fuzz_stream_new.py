@@ -5,7 +5,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
 import numpy as np
 import look_cases as K
-import test_gpu_stream as T
+import stream_util as T
 from x264_vs2008_amd import lib as L
 
 hip = L.load()

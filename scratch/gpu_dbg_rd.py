@@ -7,8 +7,8 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(
 from oracle import refslice as rs
 from oracle.gen_golden_slice import CASES2, case_inputs
 from x264_vs2008_amd import lib as L
-from test_gpu_slice_rd import run_chain2
-from test_gpu_slice import STATE
+from slice_util import run_chain2
+from slice_util import STATE
 import subprocess
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "oracle")])

@@ -129,3 +129,12 @@ def compare(hip, twin, cqm, i):
     finally:
         enc.close()
     return what, diffs, [int(want["mb_type"][f, -1]) for f in range(frames)]
+
+
+# tests/test_oracle_random_chains.py (twin == reference; oracle/gen_golden_ref_offline.py stores the reference's side): the decision arrays compared, and
+# the seeds the GPU test runs (so that both hops cover the same configurations) and a spread of others
+ARRAYS = ("mb_type", "mv", "ref", "qp", "cbp")
+SEEDS = [0, 45, 3, 7, 11, 19, 23, 58, 59, 101, 137, 1002, 1019, 1040, 1071, 1153, 1234, 1300, 1411, 1502, 1507, 1511, 1520,
+         1, 2, 64, 77, 1600, 1777, 2001, 2500,
+         # subme 8-9 (RD refinement), sub-8x8 partitions under the RD levels: 30156 is the chain that showed the cache entries a macroblock inherits
+         30000, 30001, 30003, 30006, 30011, 30013, 30019, 30021, 30023, 30156, 31003, 31404]

@@ -98,3 +98,15 @@ def compare(mine, ref):
             elif a is not None and not np.array_equal(a, b):
                 bad.append("coded frame %d list %d: %d lowres vectors differ" % (i, l, int((a != b).any(1).sum())))
     return bad
+
+
+# tests/test_lookahead_host.py's further seeds, with and without --pre-scenecut (oracle/gen_golden_ref_offline.py stores the reference's runs of them)
+LIVE_SEEDS = list(range(200, 236))
+POST_SEEDS = [11, 13, 14, 15, 19, 20, 26, 36, 37, 201, 208, 209, 214, 226, 229]
+
+
+def post_config(seed):
+    c = dict(config(seed), pre_scenecut=0)
+    if c["scenecut_threshold"] < 0:
+        c["scenecut_threshold"] = 40
+    return c

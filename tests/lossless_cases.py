@@ -14,10 +14,10 @@ import sys
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from paths import GOLDEN, ROOT
+
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
-GOLDEN = os.path.join(ROOT, "tests", "golden")
 
 ME_HEX, ME_UMH = 1, 2
 BASE = dict(qp=0, cabac=1, deblock=1, intra=0x3)

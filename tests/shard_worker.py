@@ -5,7 +5,8 @@ import sys
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from paths import ROOT
+
 sys.path.insert(0, ROOT)
 
 import torch.distributed as dist                    # noqa: E402  (CPU tensors / objects only: torch.cuda is never touched)

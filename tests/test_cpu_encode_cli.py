@@ -1,46 +1,14 @@
 """The command line front end (x264_vs2008_amd/encode.py) without a GPU: its option parser against the REFERENCE's own x264_param_parse fed the
 same options (x264_param2string of both, before validation), and the raw I420 / YUV4MPEG2 readers (R/muxers.c)."""
-import ctypes as C
 import os
 
 import numpy as np
 import pytest
 
+from mux_cases import ARGS, reference_string
+from paths import REF_SO, ROOT
 from x264_vs2008_amd import encode as E
 from x264_vs2008_amd import mux, synth
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF_SO = os.path.join(ROOT, "oracle", "_ref", "libx264ref.so")
-
-ARGS = {
-    "UF": "--qp 26 --no-cabac --me dia --subme 0 --partitions none --no-deblock --aq-mode 0 --scenecut -1 --ref 1 --bframes 0 --b-adapt 0",
-    "MED": "--crf 23 --ref 3 --bframes 3 --b-adapt 1 --me hex --subme 7 --8x8dct --partitions p8x8,b8x8,i8x8,i4x4 --trellis 1 --weightb --mixed-refs --direct spatial",
-    "SLOW": "--crf 23 --ref 5 --bframes 3 --b-adapt 2 --me umh --subme 8 --8x8dct --partitions p8x8,b8x8,i8x8,i4x4 --trellis 1 --weightb --mixed-refs --direct auto --pre-scenecut",
-    "misc": "--qp 31 --ref 4 --bframes 2 --b-bias 10 --me esa --merange 24 --subme 9 --psy-rd 0.4:0.2 --trellis 2 --deblock=-1:2 --nr 100 --cqm jvt --chroma-qp-offset 3 "
-            "--keyint 48 --min-keyint 6 --scenecut 30 --ipratio 1.2 --pbratio 1.5 --no-chroma-me --no-dct-decimate --deadzone-inter 12 --deadzone-intra 7 --partitions all",
-    "crf_misc": "--crf 18.5 --qcomp 0.75 --qpmin 12 --qpmax 44 --qpstep 6 --aq-strength 0.7 --bframes 1 --no-cabac --no-fast-pskip --deblock 2 --psy-rd 0.8 --direct temporal",
-}
-
-
-def reference_string(args):
-    from oracle import hostpic
-    ref = hostpic.load_lazy(REF_SO)
-    ref.x264_param2string.restype = C.c_void_p
-    buf = C.create_string_buffer(16384)
-    ref.x264_param_default(buf)
-    toks = args.split()
-    i = 0
-    while i < len(toks):
-        name = toks[i][2:]
-        val = None
-        if "=" in name:
-            name, val = name.split("=", 1)
-        elif i + 1 < len(toks) and not toks[i + 1].startswith("--"):
-            val = toks[i + 1]
-            i += 1
-        i += 1
-        assert ref.x264_param_parse(buf, name.encode(), None if val is None else val.encode()) == 0, (name, val)
-    return C.string_at(ref.x264_param2string(buf, 0)).decode()
 
 
 @pytest.mark.parametrize("name", sorted(ARGS))

@@ -15,24 +15,12 @@ import numpy as np
 import pytest
 
 import mux_cases as M
+from mux_cases import CLI
+from paths import REF_SO, ROOT
 from x264_vs2008_amd import mux
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF_SO = os.path.join(ROOT, "oracle", "_ref", "libx264ref.so")
 need_ref = pytest.mark.skipif(not os.path.exists(REF_SO), reason="oracle/_ref/libx264ref.so not built (needs /root/reference)")
 
-CLI = {
-    "UF": [("qp", "26"), ("no-cabac", None), ("me", "dia"), ("subme", "0"), ("partitions", "none"), ("no-deblock", None), ("aq-mode", "0"), ("scenecut", "-1"),
-           ("ref", "1"), ("bframes", "0"), ("b-adapt", "0")],
-    "MED": [("crf", "23"), ("ref", "3"), ("bframes", "3"), ("b-adapt", "1"), ("me", "hex"), ("subme", "7"), ("8x8dct", None), ("partitions", "p8x8,b8x8,i8x8,i4x4"),
-            ("trellis", "1"), ("weightb", None), ("mixed-refs", None), ("direct", "spatial")],
-    "SLOW": [("crf", "23"), ("ref", "5"), ("bframes", "3"), ("b-adapt", "2"), ("me", "umh"), ("subme", "8"), ("8x8dct", None), ("partitions", "p8x8,b8x8,i8x8,i4x4"),
-             ("trellis", "1"), ("weightb", None), ("mixed-refs", None), ("direct", "auto"), ("pre-scenecut", None)],
-    "misc": [("qp", "31"), ("ref", "4"), ("bframes", "2"), ("b-bias", "10"), ("me", "esa"), ("merange", "24"), ("subme", "9"), ("psy-rd", "0.4:0.2"), ("trellis", "2"),
-             ("deblock", "-1:2"), ("nr", "100"), ("cqm", "jvt"), ("chroma-qp-offset", "3"), ("keyint", "48"), ("min-keyint", "6"), ("scenecut", "30"), ("ipratio", "1.2"),
-             ("pbratio", "1.5"), ("no-chroma-me", None), ("no-dct-decimate", None), ("deadzone-inter", "12"), ("deadzone-intra", "7")],
-    "crf_misc": [("crf", "18.5"), ("qcomp", "0.75"), ("qpmin", "12"), ("qpmax", "44"), ("qpstep", "6"), ("aq-strength", "0.7"), ("bframes", "1"), ("no-cabac", None)],
-}
 OURS = {
     "UF": dict(M.UF, intra=3),                   # before validation the reference's param.analyse.intra is still 0x3
     "MED": M.MED,

@@ -8,11 +8,11 @@ import subprocess
 import numpy as np
 import pytest
 
+from paths import ROOT
 from x264_vs2008_amd import lib as L, synth
 from x264_vs2008_amd import slice as sl
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 @pytest.mark.parametrize("bframes", [0, 3])

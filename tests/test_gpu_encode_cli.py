@@ -7,25 +7,14 @@ import os
 import pytest
 
 import mux_cases as M
+from mux_cases import write_clip
+from paths import REF_SO
 from x264_vs2008_amd import encode as E
-from x264_vs2008_amd import mux, synth
+from x264_vs2008_amd import mux
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF_SO = os.path.join(ROOT, "oracle", "_ref", "libx264ref.so")
 UF = "--qp 26 --no-cabac --me dia --subme 0 --partitions none --no-deblock --aq-mode 0 --scenecut -1 --ref 1 --bframes 0 --b-adapt 0 --no-asm --threads 1"
 MED = "--crf 23 --ref 3 --bframes 3 --b-adapt 1 --me hex --subme 7 --8x8dct --partitions p8x8,b8x8,i8x8,i4x4 --trellis 1 --weightb --mixed-refs --direct spatial"
-
-
-def write_clip(path, w, h, n, t0=0, y4m=False):
-    with open(path, "wb") as f:
-        if y4m:
-            f.write(b"YUV4MPEG2 W%d H%d F25:1 Ip A0:0 C420jpeg\n" % (w, h))
-        for t in range(n):
-            if y4m:
-                f.write(b"FRAME\n")
-            for pl in synth.frame(w, h, t0 + t):
-                f.write(pl.tobytes())
 
 
 @pytest.mark.parametrize("y4m", [False, True])

@@ -9,9 +9,9 @@ import os
 import pytest
 
 from fuzz_b import compare
+from paths import ROOT
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 # seeds from 30000: subme 6..9 (tests/fuzz_b.py: config_refine) -- the RD refinement of subme 8-9 in I / P chains, B chains at subme 8; what the sweep

@@ -16,12 +16,11 @@ import lossless_cases as LC
 from conftest import GOLDEN
 from oracle.gen_golden_slice import case_inputs
 from x264_vs2008_amd import slice as sl
+from paths import REF_SO
+from slice_util import run_chain2
 from x264_vs2008_amd.frame import DeviceArray
-from test_gpu_slice_rd import run_chain2
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF_SO = os.path.join(ROOT, "oracle", "_ref", "libx264ref.so")
 STATE = [k for k in LC.WHOLE if k not in ("mvr", "frame_info", "stat", "payload_len", "mb_bits")]
 
 

@@ -14,20 +14,19 @@ import pytest
 import look_cases as K
 import lossless_cases as LC
 from conftest import GOLDEN
+from mux_cases import write_clip
+from paths import REF_SO
+from stream_util import run_stream
 from x264_vs2008_amd import encode as E
 from x264_vs2008_amd import lookahead as LA
 from x264_vs2008_amd import mux
 from x264_vs2008_amd.frame import FrameCtx
-from test_gpu_stream import run_stream
-from test_gpu_encode_cli import write_clip
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF_SO = os.path.join(ROOT, "oracle", "_ref", "libx264ref.so")
 
 
 def check(got, a, c, what):
-    """test_gpu_stream.check with the payloads held by their md5."""
+    """stream_util.check with the payloads held by their md5."""
     frames = c["frames"]
     assert len(got) == frames, "%s: %d frames coded, the reference codes %d" % (what, len(got), frames)
     for f, (frame, st, qp, payload) in enumerate(got):

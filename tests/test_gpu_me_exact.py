@@ -9,9 +9,8 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN
-from frame_util import make_clip_frame
+from frame_util import ME_CASES, make_clip_frame
 from oracle import hostpic
-from test_oracle_frame_golden import ME_CASES
 from x264_vs2008_amd.frame import DeviceArray, FrameCtx, Me16Params, cost_mv_table
 from x264_vs2008_amd.pipeline import LAMBDA_TAB
 

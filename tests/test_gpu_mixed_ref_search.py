@@ -11,8 +11,7 @@ import pytest
 from conftest import ROOT
 from oracle import refslice as rs
 from oracle.gen_golden_slice import case_inputs, masked
-from test_gpu_slice import check_frame
-from test_gpu_slice_rd import run_chain2
+from slice_util import check_frame, run_chain2
 
 pytestmark = pytest.mark.gpu
 

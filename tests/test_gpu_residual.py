@@ -9,7 +9,7 @@ import numpy as np
 import pytest
 
 from frame_util import HostPic, make_clip_frame
-from test_gpu_me import _setup
+from frame_util import me_setup_pair as _setup
 from x264_vs2008_amd.frame import CqmDevice, DeviceArray, chroma_qp
 
 pytestmark = pytest.mark.gpu

@@ -9,10 +9,10 @@ import numpy as np
 import pytest
 
 from oracle import refslice as rs
+from paths import REF_SO, ROOT
 from x264_vs2008_amd import shard, synth
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 OPTS = dict(qp=27, me_method=1, subme=7, n_refs=2, inter=0x13, intra=0x3, transform8x8=1, mixed_refs=1, cabac=1, deblock=1)
 EXT = dict(trellis=1, psy_rd=1.0, aq_mode=1)
 
@@ -45,9 +45,6 @@ def test_two_process_gloo_shard():
                        stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=600)
     out = r.stdout.decode(errors="replace")
     assert r.returncode == 0 and "equal" in out, out[-2000:]
-
-
-REF_SO = os.path.join(ROOT, "oracle", "_ref", "libx264ref.so")
 
 
 @pytest.mark.skipif(not os.path.exists(REF_SO), reason="oracle/_ref/libx264ref.so not built (needs /root/reference)")

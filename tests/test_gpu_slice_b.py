@@ -29,7 +29,7 @@ def test_b_slices_match_reference_loop_and_payload(hip_lib, cqm, name, size, fra
     y, u, v = case_inputs(size, frames, kind)
     kw, ekw = dict(kw), dict(ekw)
     kw.pop("cqm_preset", 0)
-    from test_gpu_slice_rd import lowres_arrays
+    from slice_util import lowres_arrays
     lowres = lowres_arrays(hip_lib, ekw.pop("lowres_seed", None), frames, size)
     enc = sl.ChainEncoder(hip_lib, size[0], size[1], cqm, batch=1, write=1, **kw, **{k: v_ for k, v_ in ekw.items() if k != "write"})
     order = sl.coding_order(frames, kw.get("keyint", 0), ekw["bframes"])

@@ -38,8 +38,7 @@ def test_twin_matches_reference_hashes(oracle_lib, name, size, frames, kw, ekw):
 @pytest.mark.gpu
 @pytest.mark.parametrize("name,size,frames,kw,ekw", HASH_CASES, ids=[c[0] for c in HASH_CASES])
 def test_gpu_matches_reference_hashes(hip_lib, cqm, name, size, frames, kw, ekw):
-    from test_gpu_slice import STATE, run_chain
-    from test_gpu_slice_rd import run_chain2
+    from slice_util import STATE, run_chain, run_chain2
     want = load(name)
     y, u, v = rs.clip(size[0], size[1], frames)
     out = run_chain(hip_lib, cqm, size, frames, y, u, v, kw) if ekw is None else run_chain2(hip_lib, cqm, size, frames, y, u, v, kw, ekw)

@@ -14,16 +14,14 @@ import pytest
 
 import look_cases as K
 import look_util as U
+from look_cases import LIVE_SEEDS, POST_SEEDS, post_config
 from oracle import refslice as rs
+from paths import REF_SO, ROOT
 from x264_vs2008_amd import lib as L
 from x264_vs2008_amd import lookahead as LA
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF_SO = os.path.join(ROOT, "oracle", "_ref", "libx264ref.so")
 GOLD = np.load(os.path.join(ROOT, "tests", "golden", "look_host.npz"))
 FIXTURE = os.path.join(ROOT, "tests", "golden", "ref_offline.npz")
-LIVE_SEEDS = list(range(200, 236))
-POST_SEEDS = [11, 13, 14, 15, 19, 20, 26, 36, 37, 201, 208, 209, 214, 226, 229]
 
 
 def stored_records(g, prefix):
@@ -31,13 +29,6 @@ def stored_records(g, prefix):
     head, qavg, mv = g[prefix + "_head"], g[prefix + "_qavg"], g[prefix + "_mv"]
     return [dict(frame=int(h[0]), slice=int(h[1]), poc=int(h[2]), qp=int(h[3]), satd=int(h[4]), f_qp_avg=float(q),
                  mv0=m[0] if h[5] else None, mv1=m[1] if h[6] else None) for h, q, m in zip(head, qavg, mv)]
-
-
-def post_config(seed):
-    c = dict(K.config(seed), pre_scenecut=0)
-    if c["scenecut_threshold"] < 0:
-        c["scenecut_threshold"] = 40
-    return c
 
 
 def run_mine(c, log=None, speculative=True):

@@ -4,7 +4,7 @@ mirror: no spilled registers, at most 64 bytes of private segment (test_no_kerne
 24 KiB.  The lookahead's SAD kernels sit beside the SATD ones."""
 import re
 
-from test_build_resources import RASTER, kernel_metadata
+from kernel_meta import RASTER, kernel_metadata
 
 
 def demangled_bools(name):

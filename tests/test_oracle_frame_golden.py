@@ -10,14 +10,11 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN
+from frame_util import ME_CASES
 from oracle import hostpic
 
 SIZES = [(352, 288), (200, 120)]
 ENC_CASES = [((352, 288), 24, 0, 0), ((352, 288), 27, 1, 0), ((200, 120), 33, 1, 1), ((200, 120), 14, 0, 0)]
-
-
-ME_CASES = [((352, 288), 1, 16, 7, 1, 26), ((352, 288), 0, 16, 5, 1, 30), ((200, 120), 1, 16, 2, 0, 22), ((200, 120), 1, 8, 1, 0, 36),
-            ((352, 288), 1, 16, 3, 1, 40), ((200, 120), 0, 16, 0, 0, 26)]
 
 
 def me_setup(lib, prefix, size):

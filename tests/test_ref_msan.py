@@ -8,7 +8,8 @@ import sys
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from paths import ROOT
+
 REF = "/root/reference/x264-snapshot-20090216-2245"
 CLANG = "/opt/rocm/lib/llvm/bin/clang"
 

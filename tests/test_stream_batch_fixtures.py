@@ -1,4 +1,5 @@
-"""CPU: the reference outputs tests/test_gpu_full_batch.py holds every chain to (tests/golden/stream_batch_{med,slow}.npz, cavlc_batch_uf.npz).
+"""CPU: the reference outputs tests/test_gpu_full_batch.py holds every chain to (tests/golden/stream_batch_{med,slow}.npz, cavlc_batch_uf.npz;
+the cases: tests/full_batch_util.py).
   * they still describe what that test needs: one record per input picture of every clip, I/P and B pictures mixed, for SLOW both
     direct modes among the B slices (else the batch's guards could pass on content that does not exercise them);
   * where oracle/_ref is built: oracle/gen_golden_stream.py and oracle/gen_golden_cavlc.py write them again byte for byte."""
@@ -7,11 +8,10 @@ import os
 import numpy as np
 import pytest
 
+import full_batch_util as T
 from oracle import refslice as rs
 from oracle.gen_golden_stream import save_npz
-import test_gpu_full_batch as T
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from paths import ROOT
 
 
 @pytest.mark.parametrize("name", sorted(T.FLAGS))
