@@ -7,9 +7,9 @@
 //   x264_rc_analyse_slice                  R/encoder/slicetype.c:638-680
 //   x264_ratecontrol_new / _start / _end   R/encoder/ratecontrol.c:268-420, 792-870, 1077-1160; rate_estimate_qscale :1396-1615
 #include <math.h>
+#include <stdint.h>
 #include <stdlib.h>
 #include <string.h>
-#include <stdio.h>
 #include "x264hip.h"
 
 namespace {
@@ -51,22 +51,51 @@ struct RC {                                   // x264_ratecontrol_t, the types o
     int bframes;
 };
 
+// A queue of pictures (pointers into the ring) in order, with its count: x264_frame_push / _unshift / _shift / _sort, R/common/frame.c:926-975
+template <int CAP> struct Queue {
+    LF *f[CAP];
+    int n;
+    LF *operator[](int i) const { return f[i]; }
+    void push(LF *x) { f[n++] = x; }
+    void unshift(LF *x) { memmove(f + 1, f, n++ * sizeof(*f)); f[0] = x; }
+    LF *shift(int at = 0) { LF *x = f[at]; n--; memmove(f + at, f + at + 1, (n - at) * sizeof(*f)); return x; }
+    void sort(bool by_type)
+    {   // by input number, or by type then input number: exchanges of neighbours until none is left, so equal keys keep their order
+        for (bool ok = false; !ok;) {
+            ok = true;
+            for (int i = 0; i + 1 < n; i++) {
+                const int dtype = f[i]->type - f[i + 1]->type, dtime = f[i]->frame - f[i + 1]->frame;
+                if (by_type ? dtype > 0 || (dtype == 0 && dtime > 0) : dtime > 0) { LF *t = f[i]; f[i] = f[i + 1]; f[i + 1] = t; ok = false; }
+            }
+        }
+    }
+};
+
+// Everything x264hip_lookahead_put / _get / _end / _scenecut change beside the ring's records: what x264hip_lookahead_save copies and _restore brings
+// back, as one assignment.  A field a decision can change belongs HERE; what is fixed at creation or rebuilt by every get() stays outside.
+struct QueueState {
+    Queue<MAX_LENGTH + 8> next, current;       // frames.next (undecided, input order), frames.current (decided, coding order)
+    Queue<16 + 2> reference;                   // the DPB
+    LF *last_nonb, *fenc, *fref0[16 + 2], *fref1[16 + 2];
+    int n_ref0, n_ref1;
+    int i_input, i_last_idr, i_frame;
+    int slice_type;
+    bool started;
+    bool setup;                                // fenc's type-dependent state (last IDR, reference lists, POC) is in place
+    int frame_num_reset;                       // the frame handed out is a scene-cut IDR: x264_encoder_encode restarts h->i_frame_num for it (encoder.c:1682)
+    RC rc;
+};
+
 }  // namespace
 
 struct x264hip_lookahead {
     x264hip_lookahead_params p;
     LF ring[RING];
-    LF *next[MAX_LENGTH + 8], *current[MAX_LENGTH + 8], *reference[16 + 2];
-    LF *last_nonb, *fenc, *fref0[16 + 2], *fref1[16 + 2];
-    int n_ref0, n_ref1;
-    int i_input, i_last_idr, i_frame, i_delay, i_max_dpb, i_max_ref1;
-    int slice_type;
-    bool started, miss;
-    bool setup;                                // la->fenc's type-dependent state (last IDR, reference lists, POC) is in place
-    int frame_num_reset;                       // the frame handed out is a scene-cut IDR: x264_encoder_encode restarts h->i_frame_num for it (encoder.c:1682)
+    QueueState q;
+    int i_delay, i_max_dpb, i_max_ref1;
+    bool miss;
     x264hip_look_need needs[16];
     int n_needs;
-    RC rc;
 };
 
 namespace {
@@ -77,11 +106,6 @@ inline double qp2qscale(double qp) { return 0.85 * pow(2.0, (qp - 12.0) / 6.0); 
 inline double qscale2qp(double qscale) { return 12.0 + 6.0 * log(qscale / 0.85) / log(2.0); }
 inline double clip3f(double v, double lo, double hi) { return v < lo ? lo : v > hi ? hi : v; }
 inline int clip3(int v, int lo, int hi) { return v < lo ? lo : v > hi ? hi : v; }
-
-int list_len(LF **l) { int n = 0; while (l[n]) n++; return n; }
-void list_push(LF **l, LF *f) { int n = list_len(l); l[n] = f; l[n + 1] = nullptr; }           // x264_frame_push
-LF *list_shift(LF **l) { LF *f = l[0]; int i; for (i = 0; l[i]; i++) l[i] = l[i + 1]; return f; }   // x264_frame_shift
-LF *list_pop(LF **l) { int n = list_len(l); LF *f = l[n - 1]; l[n - 1] = nullptr; return f; }
 
 int num_mbs(const LA *la)
 {   // NUM_MBS, slicetype.c:251-254
@@ -126,57 +150,48 @@ int frame_cost(LA *la, LF **frames, int p0, int p1, int b, int b_intra_penalty)
     return score;
 }
 
-int path_cost(LA *la, LF **frames, char *path, int threshold)
-{   // x264_slicetype_path_cost, slicetype.c:359-391
-    int loc = 1, cost = 0, cur_p = 0;
-    path--;
-    while (path[loc]) {
-        int next_p = loc, next_b;
-        while (path[next_p] && path[next_p] != 'P') next_p++;
-        if (path[next_p] != 'P') return cost;
+// The trellis of b-adapt 2 (x264_slicetype_path_search, slicetype.c:359-435).  A path over the pictures 1..n is a uint64_t: bit i - 1 is set where
+// picture i is a P, clear where it is a B.  Every path priced ends in a P (its highest set bit is bit n - 1), and n <= MAX_LENGTH - 1 = 63.
+int path_cost(LA *la, LF **frames, uint64_t path, int threshold)
+{   // from P to P (the set bits, lowest first): the P picture's cost, then the B pictures' between the two; over the threshold the path has lost
+    int cost = 0, cur_p = 0;
+    for (; path; path &= path - 1) {
+        const int next_p = __builtin_ctzll(path) + 1;
         cost += frame_cost(la, frames, cur_p, next_p, next_p, 0);
         if (la->miss) return cost;
         if (cost > threshold) break;
-        for (next_b = loc; next_b < next_p && cost < threshold; next_b++) {
-            cost += frame_cost(la, frames, cur_p, next_p, next_b, 0);
+        for (int b = cur_p + 1; b < next_p && cost < threshold; b++) {
+            cost += frame_cost(la, frames, cur_p, next_p, b, 0);
             if (la->miss) return cost;
         }
-        loc = next_p + 1;
         cur_p = next_p;
     }
     return cost;
 }
 
-void slicetype_path(LA *la, LF **frames, int length, int max_bframes, char (*best_paths)[MAX_LENGTH])
-{   // x264_slicetype_path, slicetype.c:395-426
-    char paths[BF_MAX + 2][MAX_LENGTH];
-    memset(paths, 0, sizeof(paths));
-    int num_paths = max_bframes + 1 < length ? max_bframes + 1 : length;
-    int best_cost = COST_MAX, best_path_index = 0;
+void slicetype_path(LA *la, LF **frames, int length, int max_bframes, uint64_t *best)
+{   // best[length] from the best shorter paths: each followed by s B pictures and a P, s = 0, 1, ...; the first of the cheapest wins
+    const int num_paths = max_bframes + 1 < length ? max_bframes + 1 : length;
+    int best_cost = COST_MAX, best_s = 0;
     length = length < MAX_LENGTH ? length : MAX_LENGTH;
-    for (int suffix_size = 0; suffix_size < num_paths; suffix_size++) {
-        memcpy(paths[suffix_size], best_paths[length - (suffix_size + 1)], length - (suffix_size + 1));
-        for (int loc = 0; loc < suffix_size; loc++) strcat(paths[suffix_size], "B");
-        strcat(paths[suffix_size], "P");
-    }
-    for (int path = 0; path < num_paths; path++) {
-        int cost = path_cost(la, frames, paths[path], best_cost);
+    const uint64_t last_p = 1ull << (length - 1);
+    for (int s = 0; s < num_paths; s++) {
+        const int cost = path_cost(la, frames, best[length - 1 - s] | last_p, best_cost);
         if (la->miss) return;
-        if (cost < best_cost) { best_cost = cost; best_path_index = path; }
+        if (cost < best_cost) { best_cost = cost; best_s = s; }
     }
-    memcpy(best_paths[length], paths[best_path_index], length);
+    best[length] = best[length - 1 - best_s] | last_p;
 }
 
 int path_search(LA *la, LF **frames, int length, int bframes)
-{   // x264_slicetype_path_search, slicetype.c:428-435
-    static thread_local char best_paths[MAX_LENGTH][MAX_LENGTH];
-    memset(best_paths, 0, sizeof(best_paths));
-    best_paths[1][0] = 'P';
+{   // how many B pictures the best path over the pictures before the last one starts with
+    uint64_t best[MAX_LENGTH];
+    best[0] = 0; best[1] = 1;
     for (int n = 2; n < length - 1; n++) {
-        slicetype_path(la, frames, n, bframes, best_paths);
+        slicetype_path(la, frames, n, bframes, best);
         if (la->miss) return 0;
     }
-    return (int)strspn(best_paths[length - 2], "B");
+    return best[length - 2] ? __builtin_ctzll(best[length - 2]) : 0;                             // (two pictures waiting: the empty path)
 }
 
 int scenecut(const LA *la, const LF *frame, int pdist)
@@ -184,7 +199,7 @@ int scenecut(const LA *la, const LF *frame, int pdist)
     int icost = frame->cost_est[0][0];
     int pcost = frame->cost_est[pdist][0];
     float f_bias;
-    int i_gop_size = frame->frame - la->i_last_idr;
+    int i_gop_size = frame->frame - la->q.i_last_idr;
     float f_thresh_max = la->p.scenecut_threshold / 100.0;
     float f_thresh_min = f_thresh_max * la->p.keyint_min / (la->p.keyint_max * 4);
     if (la->p.keyint_min == la->p.keyint_max) f_thresh_min = f_thresh_max;
@@ -204,14 +219,14 @@ void slicetype_analyse(LA *la)
     const int i_mb_count = num_mbs(la);
     int cost1p0, cost2p0, cost1b1, cost2p1, idr_frame_type;
 
-    if (!la->last_nonb) return;
-    frames[0] = la->last_nonb;
-    for (j = 0; la->next[j] && la->next[j]->type == T_AUTO; j++) frames[j + 1] = la->next[j];
-    keyint_limit = la->p.keyint_max - frames[0]->frame + la->i_last_idr - 1;
+    if (!la->q.last_nonb) return;
+    frames[0] = la->q.last_nonb;
+    for (j = 0; j < la->q.next.n && la->q.next[j]->type == T_AUTO; j++) frames[j + 1] = la->q.next[j];
+    keyint_limit = la->p.keyint_max - frames[0]->frame + la->q.i_last_idr - 1;
     num_frames = j < keyint_limit ? j : keyint_limit;
     if (num_frames == 0) return;
 
-    idr_frame_type = frames[1]->frame - la->i_last_idr >= la->p.keyint_min ? T_IDR : T_I;
+    idr_frame_type = frames[1]->frame - la->q.i_last_idr >= la->p.keyint_min ? T_IDR : T_I;
 
     if (num_frames == 1) {
 no_b_frames:
@@ -280,18 +295,18 @@ speculate:
 
 void slicetype_decide(LA *la)
 {   // x264_slicetype_decide, slicetype.c:577-636
-    if (!la->next[0]) return;
+    if (!la->q.next.n) return;
     if ((la->p.bframes && la->p.b_adapt) || la->p.pre_scenecut) slicetype_analyse(la);
     if (la->miss) return;
     for (int bframes = 0;; bframes++) {
-        LF *frm = la->next[bframes];
-        if (frm->frame - la->i_last_idr >= la->p.keyint_max) {
+        LF *frm = la->q.next[bframes];
+        if (frm->frame - la->q.i_last_idr >= la->p.keyint_max) {
             if (frm->type == T_AUTO) frm->type = T_IDR;
         }
         if (frm->type == T_IDR) {
-            if (bframes > 0) { bframes--; la->next[bframes]->type = T_P; }
+            if (bframes > 0) { bframes--; la->q.next[bframes]->type = T_P; }
         }
-        if (bframes == la->p.bframes || la->next[bframes + 1] == nullptr) {
+        if (bframes == la->p.bframes || bframes + 1 == la->q.next.n) {
             if (frm->type == T_AUTO || IS_TYPE_B(frm->type)) frm->type = T_P;
         }
         if (frm->type == T_AUTO) frm->type = T_B;
@@ -302,7 +317,7 @@ void slicetype_decide(LA *la)
 // ---- rate control ----------------------------------------------------------------------------------------------------------------
 void rc_new(LA *la)
 {   // x264_ratecontrol_new, ratecontrol.c:268-377
-    RC *rc = &la->rc;
+    RC *rc = &la->q.rc;
     const x264hip_lookahead_params *p = &la->p;
     memset(rc, 0, sizeof(*rc));
     rc->b_abr = p->rc_method != 0;
@@ -339,7 +354,7 @@ void rc_new(LA *la)
 
 double get_qscale(LA *la, int tex_bits, int mv_bits, float blurred_complexity, double rate_factor)
 {   // ratecontrol.c:1168-1195 (no zones)
-    RC *rcc = &la->rc;
+    RC *rcc = &la->q.rc;
     double q = pow((double)blurred_complexity, (double)(1 - la->p.qcompress));     // C: pow(double(float), double(float))
     if (!isfinite(q) || tex_bits + mv_bits == 0)
         q = rcc->last_qscale;
@@ -354,19 +369,19 @@ double get_qscale(LA *la, int tex_bits, int mv_bits, float blurred_complexity, d
 float rate_estimate_qscale(LA *la, int satd)
 {   // ratecontrol.c:1396-1615, the B branch and the 1-pass branch with CRF; no VBV: clip_qscale is the clip to lmin / lmax
     float q;
-    RC *rcc = &la->rc;
-    const int pict_type = la->slice_type;
+    RC *rcc = &la->q.rc;
+    const int pict_type = la->q.slice_type;
     const x264hip_lookahead_params *p = &la->p;
     if (pict_type == ST_B) {
-        const LF *r0 = la->fref0[0], *r1 = la->fref1[0];
+        const LF *r0 = la->q.fref0[0], *r1 = la->q.fref1[0];
         int i0 = IS_TYPE_I(r0->type), i1 = IS_TYPE_I(r1->type);
-        int dt0 = abs(la->fenc->poc - r0->poc), dt1 = abs(la->fenc->poc - r1->poc);
+        int dt0 = abs(la->q.fenc->poc - r0->poc), dt1 = abs(la->q.fenc->poc - r1->poc);
         float q0 = r0->f_qp_avg_rc, q1 = r1->f_qp_avg_rc;
         if (i0 && i1) q = (q0 + q1) / 2 + rcc->ip_offset;
         else if (i0) q = q1;
         else if (i1) q = q0;
         else q = (q0 * dt1 + q1 * dt0) / (dt0 + dt1);
-        if (la->fenc->kept_as_ref) q += rcc->pb_offset / 2;
+        if (la->q.fenc->kept_as_ref) q += rcc->pb_offset / 2;
         else q += rcc->pb_offset;
         rcc->last_satd = 0;
         return qp2qscale(q);
@@ -382,7 +397,7 @@ float rate_estimate_qscale(LA *la, int satd)
         if (pict_type == ST_I && p->keyint_max > 1 && rcc->last_non_b_pict_type != ST_I) {
             q = qp2qscale(rcc->accum_p_qp / rcc->accum_p_norm);
             q /= fabs((double)p->ip_factor);
-        } else if (la->i_frame > 0) {
+        } else if (la->q.i_frame > 0) {
             double lmin = rcc->last_qscale_for[pict_type] / rcc->lstep;
             double lmax = rcc->last_qscale_for[pict_type] * rcc->lstep;
             q = clip3f(q, lmin, lmax);
@@ -396,45 +411,45 @@ float rate_estimate_qscale(LA *la, int satd)
             q = qq;
         }
         rcc->last_qscale_for[pict_type] = rcc->last_qscale = q;
-        if (la->fenc->frame == 0) rcc->last_qscale_for[ST_P] = q;
+        if (la->q.fenc->frame == 0) rcc->last_qscale_for[ST_P] = q;
         return q;
     }
 }
 
 void rc_start(LA *la, int satd)
 {   // x264_ratecontrol_start, ratecontrol.c:792-870
-    RC *rc = &la->rc;
+    RC *rc = &la->q.rc;
     float q;
-    if (la->slice_type != ST_B) {
+    if (la->q.slice_type != ST_B) {
         rc->bframes = 0;
-        while (la->current[rc->bframes] && IS_TYPE_B(la->current[rc->bframes]->type)) rc->bframes++;
+        while (rc->bframes < la->q.current.n && IS_TYPE_B(la->q.current[rc->bframes]->type)) rc->bframes++;
     }
     if (rc->b_abr)
         q = qscale2qp(rate_estimate_qscale(la, satd));
     else {
-        if (la->slice_type == ST_B && la->fenc->kept_as_ref) q = (rc->qp_constant[ST_B] + rc->qp_constant[ST_P]) / 2;
-        else q = rc->qp_constant[la->slice_type];
+        if (la->q.slice_type == ST_B && la->q.fenc->kept_as_ref) q = (rc->qp_constant[ST_B] + rc->qp_constant[ST_P]) / 2;
+        else q = rc->qp_constant[la->q.slice_type];
     }
     rc->qpa_rc = 0;
     rc->qp = clip3((int)(q + 0.5), 0, 51);
-    la->fenc->f_qp_avg_rc = rc->qp;
+    la->q.fenc->f_qp_avg_rc = rc->qp;
     rc->f_qpm = q;
-    if (la->slice_type != ST_B) rc->last_non_b_pict_type = la->slice_type;
+    if (la->q.slice_type != ST_B) rc->last_non_b_pict_type = la->q.slice_type;
 }
 
 void rc_end(LA *la)
 {   // x264_ratecontrol_mb's running sum and x264_ratecontrol_end, ratecontrol.c:930, 1077-1135.  What depends on the frame's size in bits
     // (cplxr_sum, the size predictors) feeds ABR and VBV only and is not kept.
-    RC *rc = &la->rc;
+    RC *rc = &la->q.rc;
     rc->qpa_rc = 0;
     for (int i = 0; i < rc->nmb; i++) rc->qpa_rc += rc->f_qpm;
-    la->fenc->f_qp_avg_rc = rc->qpa_rc /= rc->nmb;
+    la->q.fenc->f_qp_avg_rc = rc->qpa_rc /= rc->nmb;
     if (rc->b_abr) {
         const float qp = rc->qpa_rc;                                                             // accum_p_qp_update( h, rc->qpa_rc ), :776-786
         rc->accum_p_qp *= .95;
         rc->accum_p_norm *= .95;
         rc->accum_p_norm += 1;
-        if (la->slice_type == ST_I) rc->accum_p_qp += qp + rc->ip_offset;
+        if (la->q.slice_type == ST_I) rc->accum_p_qp += qp + rc->ip_offset;
         else rc->accum_p_qp += qp;
     }
 }
@@ -453,7 +468,7 @@ extern "C" x264hip_lookahead *x264hip_lookahead_new(const x264hip_lookahead_para
     la->i_delay = p->b_adapt == 2 ? (p->bframes > 3 ? p->bframes : 3) * 4 : p->bframes;            // encoder.c:703-706, one thread
     la->i_max_ref1 = p->bframes ? 1 : 0;                                                         // sps->vui.i_num_reorder_frames, set.c:176
     la->i_max_dpb = 16;                                                                          // only the nearest of each list is read here
-    la->i_last_idr = -p->keyint_max;
+    la->q.i_last_idr = -p->keyint_max;
     rc_new(la);
     return la;
 }
@@ -462,12 +477,12 @@ extern "C" void x264hip_lookahead_delete(x264hip_lookahead *la) { free(la); }
 
 extern "C" int x264hip_lookahead_put(x264hip_lookahead *la)
 {
-    LF *f = &la->ring[la->i_input % RING];
+    LF *f = &la->ring[la->q.i_input % RING];
     memset(f, 0, sizeof(*f));
-    f->frame = la->i_input++;
+    f->frame = la->q.i_input++;
     f->type = T_AUTO;
     for (int i = 0; i < BF_MAX + 2; i++) for (int k = 0; k < BF_MAX + 2; k++) f->cost_est[i][k] = f->spec_cost[i][k] = -1;   // x264_frame_init_lowres, mc.c:323-330
-    list_push(la->next, f);
+    la->q.next.push(f);
     return f->frame;
 }
 
@@ -475,62 +490,62 @@ extern "C" int x264hip_lookahead_get(x264hip_lookahead *la, int flushing, x264hi
 {
     la->n_needs = 0; la->miss = false;
     if (n_need) *n_need = 0;
-    if (la->started) return -1;
-    if (!la->fenc) {
-        if (!flushing && la->i_input <= la->i_delay) return X264HIP_LOOK_NONE;                   // encoder.c:1423-1430
-        if (!la->current[0]) {
-            int bframes = 0, types[MAX_LENGTH + 8], n = 0;
-            if (!la->next[0]) return X264HIP_LOOK_END;
-            for (n = 0; la->next[n]; n++) types[n] = la->next[n]->type;
+    if (la->q.started) return -1;
+    if (!la->q.fenc) {
+        if (!flushing && la->q.i_input <= la->i_delay) return X264HIP_LOOK_NONE;                 // encoder.c:1423-1430
+        if (!la->q.current.n) {
+            int bframes = 0, types[MAX_LENGTH + 8];
+            if (!la->q.next.n) return X264HIP_LOOK_END;
+            for (int i = 0; i < la->q.next.n; i++) types[i] = la->q.next[i]->type;
             slicetype_decide(la);
             if (la->miss) {
-                for (int i = 0; i < n; i++) la->next[i]->type = types[i];
+                for (int i = 0; i < la->q.next.n; i++) la->q.next[i]->type = types[i];
                 goto needs;
             }
-            while (IS_TYPE_B(la->next[bframes]->type)) bframes++;                                // encoder.c:1444-1458
-            list_push(la->current, list_shift(&la->next[bframes]));
-            while (bframes--) list_push(la->current, list_shift(la->next));
+            while (IS_TYPE_B(la->q.next[bframes]->type)) bframes++;                              // encoder.c:1444-1458
+            la->q.current.push(la->q.next.shift(bframes));
+            while (bframes--) la->q.current.push(la->q.next.shift());
         }
-        la->fenc = list_shift(la->current);
-        la->setup = false; la->frame_num_reset = 0;
+        la->q.fenc = la->q.current.shift();
+        la->q.setup = false; la->q.frame_num_reset = 0;
     }
-    if (!la->setup) {                                                                            // do_encode:, encoder.c:1471-1530
-        LF *f = la->fenc;
-        la->setup = true;
+    if (!la->q.setup) {                                                                          // do_encode:, encoder.c:1471-1530
+        LF *f = la->q.fenc;
+        la->q.setup = true;
         if (f->type == T_IDR) {
-            la->i_last_idr = f->frame;
-            while (la->reference[0]) list_pop(la->reference);                                    // x264_reference_reset
+            la->q.i_last_idr = f->frame;
+            la->q.reference.n = 0;                                                               // x264_reference_reset
         }
-        la->slice_type = IS_TYPE_I(f->type) ? ST_I : f->type == T_P ? ST_P : ST_B;
-        f->poc = 2 * (f->frame - la->i_last_idr);
+        la->q.slice_type = IS_TYPE_I(f->type) ? ST_I : f->type == T_P ? ST_P : ST_B;
+        f->poc = 2 * (f->frame - la->q.i_last_idr);
         f->kept_as_ref = !IS_TYPE_B(f->type) && la->p.keyint_max > 1;
-        la->n_ref0 = la->n_ref1 = 0;                                                             // x264_reference_build_list
-        for (int i = 0; la->reference[i]; i++) {
-            if (la->reference[i]->poc < f->poc) la->fref0[la->n_ref0++] = la->reference[i];
-            else if (la->reference[i]->poc > f->poc) la->fref1[la->n_ref1++] = la->reference[i];
+        la->q.n_ref0 = la->q.n_ref1 = 0;                                                         // x264_reference_build_list
+        for (int i = 0; i < la->q.reference.n; i++) {
+            if (la->q.reference[i]->poc < f->poc) la->q.fref0[la->q.n_ref0++] = la->q.reference[i];
+            else if (la->q.reference[i]->poc > f->poc) la->q.fref1[la->q.n_ref1++] = la->q.reference[i];
         }
-        for (int i = 0; i < la->n_ref0; i++)
-            for (int k = i + 1; k < la->n_ref0; k++)
-                if (la->fref0[k]->poc > la->fref0[i]->poc) { LF *t = la->fref0[i]; la->fref0[i] = la->fref0[k]; la->fref0[k] = t; }
-        for (int i = 0; i < la->n_ref1; i++)
-            for (int k = i + 1; k < la->n_ref1; k++)
-                if (la->fref1[k]->poc < la->fref1[i]->poc) { LF *t = la->fref1[i]; la->fref1[i] = la->fref1[k]; la->fref1[k] = t; }
-        if (la->n_ref1 > la->i_max_ref1) la->n_ref1 = la->i_max_ref1;
+        for (int i = 0; i < la->q.n_ref0; i++)
+            for (int k = i + 1; k < la->q.n_ref0; k++)
+                if (la->q.fref0[k]->poc > la->q.fref0[i]->poc) { LF *t = la->q.fref0[i]; la->q.fref0[i] = la->q.fref0[k]; la->q.fref0[k] = t; }
+        for (int i = 0; i < la->q.n_ref1; i++)
+            for (int k = i + 1; k < la->q.n_ref1; k++)
+                if (la->q.fref1[k]->poc < la->q.fref1[i]->poc) { LF *t = la->q.fref1[i]; la->q.fref1[i] = la->q.fref1[k]; la->q.fref1[k] = t; }
+        if (la->q.n_ref1 > la->i_max_ref1) la->q.n_ref1 = la->i_max_ref1;
     }
     {
-        LF *f = la->fenc;
+        LF *f = la->q.fenc;
         int satd = 0;
-        if (la->rc.b_abr && la->slice_type != ST_B) {                                            // x264_rc_analyse_slice, slicetype.c:638-680
+        if (la->q.rc.b_abr && la->q.slice_type != ST_B) {                                        // x264_rc_analyse_slice, slicetype.c:638-680
             LF *frames[BF_MAX * 4 + 2] = {nullptr};
             int p0 = 0, p1, b;
-            if (la->slice_type == ST_I) p1 = b = 0;
+            if (la->q.slice_type == ST_I) p1 = b = 0;
             else {
                 p1 = 0;
-                while (la->current[p1] && IS_TYPE_B(la->current[p1]->type)) p1++;
+                while (p1 < la->q.current.n && IS_TYPE_B(la->q.current[p1]->type)) p1++;
                 p1++;
                 b = p1;
             }
-            frames[p0] = la->n_ref0 ? la->fref0[0] : nullptr;
+            frames[p0] = la->q.n_ref0 ? la->q.fref0[0] : nullptr;
             frames[b] = f;
             satd = frame_cost(la, frames, p0, p1, b, 0);
             if (la->miss) goto needs;
@@ -539,16 +554,16 @@ extern "C" int x264hip_lookahead_get(x264hip_lookahead *la, int flushing, x264hi
         rc_start(la, satd);
         if (out) {
             out->frame = f->frame; out->type = f->type; out->poc = f->poc; out->kept_as_ref = f->kept_as_ref;
-            out->qp = la->rc.qp; out->f_qpm = la->rc.f_qpm;
-            const bool inter = la->slice_type != ST_I;
-            out->ref0_frame = inter && la->n_ref0 ? la->fref0[0]->frame : -1;
-            out->ref1_frame = la->slice_type == ST_B && la->n_ref1 ? la->fref1[0]->frame : -1;
+            out->qp = la->q.rc.qp; out->f_qpm = la->q.rc.f_qpm;
+            const bool inter = la->q.slice_type != ST_I;
+            out->ref0_frame = inter && la->q.n_ref0 ? la->q.fref0[0]->frame : -1;
+            out->ref1_frame = la->q.slice_type == ST_B && la->q.n_ref1 ? la->q.fref1[0]->frame : -1;
             out->lowres_l0 = out->ref0_frame >= 0 && f->frame - out->ref0_frame - 1 <= BF_MAX && f->searched[0][f->frame - out->ref0_frame - 1];
             out->lowres_l1 = out->ref1_frame >= 0 && out->ref1_frame - f->frame - 1 <= BF_MAX && f->searched[1][out->ref1_frame - f->frame - 1];
             out->i_satd = f->i_satd;
-            out->frame_num_reset = la->frame_num_reset;
+            out->frame_num_reset = la->q.frame_num_reset;
         }
-        la->started = true;
+        la->q.started = true;
         return X264HIP_LOOK_FRAME;
     }
 needs:
@@ -565,7 +580,7 @@ needs:
 
 extern "C" void x264hip_lookahead_set_cost(x264hip_lookahead *la, int b, int p0, int p1, int score, int intra_mbs, int cost00, int speculative)
 {
-    if (b < 0 || b >= la->i_input || la->i_input - b > RING || b - p0 < 0 || b - p0 > BF_MAX + 1 || p1 - b < 0 || p1 - b > BF_MAX + 1) return;
+    if (b < 0 || b >= la->q.i_input || la->q.i_input - b > RING || b - p0 < 0 || b - p0 > BF_MAX + 1 || p1 - b < 0 || p1 - b > BF_MAX + 1) return;
     LF *f = &la->ring[b % RING];
     if (b != p0) f->dev_searched[0][b - p0 - 1] = true;
     if (b != p1) f->dev_searched[1][p1 - b - 1] = true;
@@ -582,32 +597,18 @@ extern "C" void x264hip_lookahead_set_cost(x264hip_lookahead *la, int b, int p0,
 
 extern "C" void x264hip_lookahead_end(x264hip_lookahead *la)
 {
-    if (!la->started) return;
+    if (!la->q.started) return;
     rc_end(la);
-    LF *f = la->fenc;
-    la->i_frame++;                                                                               // x264_reference_update, encoder.c:1062-1093
+    LF *f = la->q.fenc;
+    la->q.i_frame++;                                                                             // x264_reference_update, encoder.c:1062-1093
     if (f->kept_as_ref) {
-        if (la->slice_type != ST_B) la->last_nonb = f;
-        list_push(la->reference, f);
-        if (la->reference[la->i_max_dpb]) list_shift(la->reference);
+        if (la->q.slice_type != ST_B) la->q.last_nonb = f;
+        la->q.reference.push(f);
+        if (la->q.reference.n > la->i_max_dpb) la->q.reference.shift();
     }
-    la->fenc = nullptr;
-    la->started = false;
-    la->setup = false;
-}
-
-// x264_frame_sort (R/common/frame.c:957-975): by input number, or by type then input number
-static void list_sort(LF **l, int b_dts)
-{
-    bool ok;
-    if (!l[0]) return;
-    do {
-        ok = true;
-        for (int i = 0; l[i + 1]; i++) {
-            const int dtype = l[i]->type - l[i + 1]->type, dtime = l[i]->frame - l[i + 1]->frame;
-            if (b_dts ? dtype > 0 || (dtype == 0 && dtime > 0) : dtime > 0) { LF *t = l[i]; l[i] = l[i + 1]; l[i + 1] = t; ok = false; }
-        }
-    } while (!ok);
+    la->q.fenc = nullptr;
+    la->q.started = false;
+    la->q.setup = false;
 }
 
 // The post-encode scene cut found the P picture just coded no better than an intra picture (x264hip_scenecut_post; R/encoder/encoder.c:1645-1699): the
@@ -616,34 +617,31 @@ static void list_sort(LF **l, int b_dts)
 // the undecided queue).  Returns 1 (same picture again), 2 (another picture), -1 if no P picture is being coded.
 extern "C" int x264hip_lookahead_scenecut(x264hip_lookahead *la)
 {
-    if (!la->started || !la->fenc || la->slice_type != ST_P) return -1;
-    LF *f = la->fenc;
-    const int gop = f->frame - la->i_last_idr;
+    if (!la->q.started || !la->q.fenc || la->q.slice_type != ST_P) return -1;
+    LF *f = la->q.fenc;
+    const int gop = f->frame - la->q.i_last_idr;
     int b = 0, ret = 1;
-    while (la->current[b] && IS_TYPE_B(la->current[b]->type)) b++;
-    la->frame_num_reset = 0;
+    while (b < la->q.current.n && IS_TYPE_B(la->q.current[b]->type)) b++;
+    la->q.frame_num_reset = 0;
     if (b > 0) {
         if (la->p.b_adapt || b > 1) f->type = T_AUTO;
-        list_sort(la->current, 0);
-        int n = list_len(la->next);                                                              // x264_frame_unshift
-        la->next[n + 1] = nullptr;
-        for (int i = n; i > 0; i--) la->next[i] = la->next[i - 1];
-        la->next[0] = f;
-        la->fenc = la->current[b - 1];
-        la->current[b - 1] = nullptr;
-        la->fenc->type = T_P;
-        list_sort(la->current, 1);
+        la->q.current.sort(false);
+        la->q.next.unshift(f);
+        la->q.fenc = la->q.current[b - 1];
+        la->q.current.n = b - 1;
+        la->q.fenc->type = T_P;
+        la->q.current.sort(true);
         ret = 2;
     } else if (gop >= la->p.keyint_min) {
         f->type = T_IDR;
         f->poc = 0;
-        while (la->current[0]) list_push(la->next, list_shift(la->current));
-        list_sort(la->next, 0);
-        la->frame_num_reset = 1;
+        while (la->q.current.n) la->q.next.push(la->q.current.shift());
+        la->q.next.sort(false);
+        la->q.frame_num_reset = 1;
     } else
         f->type = T_I;
-    la->started = false;
-    la->setup = false;
+    la->q.started = false;
+    la->q.setup = false;
     return ret;
 }
 
@@ -653,11 +651,7 @@ extern "C" int x264hip_lookahead_scenecut(x264hip_lookahead *la)
 namespace {
 enum { SAVED_LF = 96 };
 struct Saved {
-    LF *next[MAX_LENGTH + 8], *current[MAX_LENGTH + 8], *reference[16 + 2];
-    LF *last_nonb, *fenc, *fref0[16 + 2], *fref1[16 + 2];
-    int n_ref0, n_ref1, i_input, i_last_idr, i_frame, slice_type, frame_num_reset;
-    bool started, setup;
-    RC rc;
+    QueueState q;
     int n_lf;
     struct { LF *f; LF copy; } lf[SAVED_LF];             // every picture a queue, the DPB or the frame in flight names: whole records (types, costs, what is "searched")
 };
@@ -666,10 +660,7 @@ extern "C" size_t x264hip_lookahead_state_bytes(void) { return sizeof(Saved); }
 extern "C" int x264hip_lookahead_save(const x264hip_lookahead *la, void *buf)
 {
     Saved *s = (Saved *)buf;
-    memcpy(s->next, la->next, sizeof(s->next)); memcpy(s->current, la->current, sizeof(s->current)); memcpy(s->reference, la->reference, sizeof(s->reference));
-    s->last_nonb = la->last_nonb; s->fenc = la->fenc; memcpy(s->fref0, la->fref0, sizeof(s->fref0)); memcpy(s->fref1, la->fref1, sizeof(s->fref1));
-    s->n_ref0 = la->n_ref0; s->n_ref1 = la->n_ref1; s->i_input = la->i_input; s->i_last_idr = la->i_last_idr; s->i_frame = la->i_frame;
-    s->slice_type = la->slice_type; s->frame_num_reset = la->frame_num_reset; s->started = la->started; s->setup = la->setup; s->rc = la->rc;
+    const QueueState &q = s->q = la->q;
     s->n_lf = 0;
     bool full = false;
     auto keep = [&](LF *f) {
@@ -678,37 +669,33 @@ extern "C" int x264hip_lookahead_save(const x264hip_lookahead *la, void *buf)
         if (s->n_lf >= SAVED_LF) { full = true; return; }
         s->lf[s->n_lf].f = f; s->lf[s->n_lf].copy = *f; s->n_lf++;
     };
-    for (int i = 0; la->next[i]; i++) keep(la->next[i]);
-    for (int i = 0; la->current[i]; i++) keep(la->current[i]);
-    for (int i = 0; la->reference[i]; i++) keep(la->reference[i]);
-    keep(la->fenc); keep(la->last_nonb);
+    for (int i = 0; i < q.next.n; i++) keep(q.next[i]);
+    for (int i = 0; i < q.current.n; i++) keep(q.current[i]);
+    for (int i = 0; i < q.reference.n; i++) keep(q.reference[i]);
+    keep(q.fenc); keep(q.last_nonb);
     return full ? -1 : 0;
 }
 // back to the saved state; pictures that came in since (x264hip_lookahead_put) are queued again as put left them, in input order
 extern "C" void x264hip_lookahead_restore(x264hip_lookahead *la, const void *buf)
 {
     const Saved *s = (const Saved *)buf;
-    const int i_input_now = la->i_input;
-    memcpy(la->next, s->next, sizeof(s->next)); memcpy(la->current, s->current, sizeof(s->current)); memcpy(la->reference, s->reference, sizeof(s->reference));
-    la->last_nonb = s->last_nonb; la->fenc = s->fenc; memcpy(la->fref0, s->fref0, sizeof(s->fref0)); memcpy(la->fref1, s->fref1, sizeof(s->fref1));
-    la->n_ref0 = s->n_ref0; la->n_ref1 = s->n_ref1; la->i_last_idr = s->i_last_idr; la->i_frame = s->i_frame;
-    la->slice_type = s->slice_type; la->frame_num_reset = s->frame_num_reset; la->started = s->started; la->setup = s->setup; la->rc = s->rc;
+    const int i_input_now = la->q.i_input;
+    la->q = s->q;                                                                                // (i_input too: the puts below count it up again)
     for (int i = 0; i < s->n_lf; i++) *s->lf[i].f = s->lf[i].copy;
-    la->i_input = s->i_input;
-    for (int n = s->i_input; n < i_input_now; n++) x264hip_lookahead_put(la);
+    for (int n = s->q.i_input; n < i_input_now; n++) x264hip_lookahead_put(la);
     la->n_needs = 0; la->miss = false;
 }
 
 extern "C" int x264hip_lookahead_oldest_live(const x264hip_lookahead *la)
 {
-    int m = la->i_input;
-    for (int i = 0; la->next[i]; i++) if (la->next[i]->frame < m) m = la->next[i]->frame;
-    for (int i = 0; la->current[i]; i++) if (la->current[i]->frame < m) m = la->current[i]->frame;
-    if (la->fenc && la->fenc->frame < m) m = la->fenc->frame;
-    if (la->last_nonb && la->last_nonb->frame < m) m = la->last_nonb->frame;
-    if (la->fenc) {
-        if (la->n_ref0 && la->fref0[0]->frame < m) m = la->fref0[0]->frame;
-        if (la->n_ref1 && la->fref1[0]->frame < m) m = la->fref1[0]->frame;
+    int m = la->q.i_input;
+    for (int i = 0; i < la->q.next.n; i++) if (la->q.next[i]->frame < m) m = la->q.next[i]->frame;
+    for (int i = 0; i < la->q.current.n; i++) if (la->q.current[i]->frame < m) m = la->q.current[i]->frame;
+    if (la->q.fenc && la->q.fenc->frame < m) m = la->q.fenc->frame;
+    if (la->q.last_nonb && la->q.last_nonb->frame < m) m = la->q.last_nonb->frame;
+    if (la->q.fenc) {
+        if (la->q.n_ref0 && la->q.fref0[0]->frame < m) m = la->q.fref0[0]->frame;
+        if (la->q.n_ref1 && la->q.fref1[0]->frame < m) m = la->q.fref1[0]->frame;
     }
     return m;
 }
