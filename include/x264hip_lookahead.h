@@ -47,8 +47,9 @@ int x264hip_event_query(void *ev);       /* 1 finished, 0 not yet, < 0 error */
  * frees -- the lookahead's short kernels beside sweeps that keep the device full */
 void *x264hip_stream_create_high_priority(void);
 /* a stream whose kernels run on compute units [first, first + n) of 256 only; x264hip_frame_ctx_set_b_stream: the stream the B kernel of
- * this context's chain-table launches runs on (default: one the library creates) -- a caller may give the step's I / P chains and its B chains
- * disjoint parts of the device (x264hip_frame_ctx_new takes the context's own stream) */
+ * this context's chain-table launches runs on (default, and again after NULL: one the library creates and x264hip_frame_ctx_delete destroys)
+ * -- a caller may give the step's I / P chains and its B chains disjoint parts of the device (x264hip_frame_ctx_new takes the context's own
+ * stream).  The stream stays the caller's: the context never destroys it, the caller does once the context is deleted or has been given another. */
 void *x264hip_stream_create_cu_range(int first_cu, int n_cus);
 int x264hip_frame_ctx_set_b_stream(x264hip_frame_ctx *c, void *hip_stream);
 /* The batch elements the end-of-frame calls of this context touch from now on -- x264hip_deblock_frame, x264hip_expand_border,

@@ -261,9 +261,8 @@ static int alloc_plane(u8 **out, int stride, int lines, int padh, int padv, int 
 {
     u8 *base = nullptr;
     HIPCHK(hipMalloc((void **)&base, bs * batch + 256));
-    if (zero_async(base, bs * batch + 256, s)) return -1;
-    *out = base + (size_t)stride * padv + padh;
-    return 0;
+    *out = base + (size_t)stride * padv + padh;        // the picture's from here on: a caller that fails later frees it with the rest
+    return zero_async(base, bs * batch + 256, s);
 }
 static void free_plane(u8 *p, int stride, int padh, int padv)
 {
@@ -297,8 +296,14 @@ extern "C" x264hip_frame_ctx *x264hip_frame_ctx_new(x264hip_frame_dims *d, void 
     if (hip_stream) { c->stream = (hipStream_t)hip_stream; c->own_stream = false; }
     else if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) { free(c); return nullptr; }
     else c->own_stream = true;
-    if (hipMalloc((void **)&c->ssd_dev, 24 * (size_t)c->batch + 64) != hipSuccess) { free(c); return nullptr; }
-    (void)hipMemset(c->ssd_dev, 0, 24 * (size_t)c->batch + 64);   // the tail holds the context's sticky sweep-abort counter (frame_slice.hip)
+    const size_t ssd_bytes = 24 * (size_t)c->batch;                // one allocation: the accumulators, then the abort counter
+    if (hipMalloc((void **)&c->ssd_dev, ssd_bytes + 64) != hipSuccess) {
+        if (c->own_stream) (void)hipStreamDestroy(c->stream);
+        free(c);
+        return nullptr;
+    }
+    (void)hipMemset(c->ssd_dev, 0, ssd_bytes + 64);
+    c->abort_total = (int *)((char *)c->ssd_dev + ssd_bytes + 32);
     return c;
 }
 extern "C" void x264hip_frame_ctx_delete(x264hip_frame_ctx *c)
@@ -306,6 +311,9 @@ extern "C" void x264hip_frame_ctx_delete(x264hip_frame_ctx *c)
     if (!c) return;
     (void)hipStreamSynchronize(c->stream);
     if (c->ssd_dev) (void)hipFree(c->ssd_dev);
+    if (c->b_ready) (void)hipEventDestroy(c->b_ready);
+    if (c->b_done) (void)hipEventDestroy(c->b_done);
+    if (c->own_b_stream) (void)hipStreamDestroy(c->b_stream);
     if (c->own_stream) (void)hipStreamDestroy(c->stream);
     free(c);
 }
@@ -324,41 +332,34 @@ extern "C" int x264hip_frame_ctx_select(x264hip_frame_ctx *c, int batch_index)
     return 0;
 }
 
-extern "C" int x264hip_picture_alloc(x264hip_frame_ctx *c, x264hip_picture *pic)
+// Y, U, V; with `hpel` the three half-pel planes, with `lowres` the four half-resolution planes.  A failure leaves what was allocated in `pic`.
+static int alloc_planes(x264hip_frame_ctx *c, x264hip_picture *pic, bool hpel, bool lowres)
 {
-    memset(pic, 0, sizeof(*pic));
     const x264hip_frame_dims &d = c->d;
     if (alloc_plane(&pic->plane[0], d.stride_y, d.lines_y, PADH, PADV, c->batch, c->bs_y, c->stream)) return -1;
     for (int i = 1; i < 3; i++)
         if (alloc_plane(&pic->plane[i], d.stride_c, d.lines_c, PADH / 2, PADV / 2, c->batch, c->bs_c, c->stream)) return -1;
     pic->filtered[0] = pic->plane[0];
-    for (int i = 1; i < 4; i++)
+    for (int i = 1; hpel && i < 4; i++)
         if (alloc_plane(&pic->filtered[i], d.stride_y, d.lines_y, PADH, PADV, c->batch, c->bs_y, c->stream)) return -1;
+    if (!lowres) return 0;
     pic->width_lowres = c->width_l; pic->lines_lowres = c->lines_l; pic->stride_lowres = c->stride_l;
     for (int i = 0; i < 4; i++)
         if (alloc_plane(&pic->lowres[i], c->stride_l, c->lines_l, PADH, PADV, c->batch, c->bs_l, c->stream)) return -1;
     return 0;
 }
-// A source picture: Y, U, V only (x264_frame_t of an input frame needs no half-pel planes; 3.5 MB per 1080p chain instead of 12.7)
-extern "C" int x264hip_picture_alloc_source(x264hip_frame_ctx *c, x264hip_picture *pic)
+static int picture_alloc(x264hip_frame_ctx *c, x264hip_picture *pic, bool hpel, bool lowres)
 {
     memset(pic, 0, sizeof(*pic));
-    const x264hip_frame_dims &d = c->d;
-    if (alloc_plane(&pic->plane[0], d.stride_y, d.lines_y, PADH, PADV, c->batch, c->bs_y, c->stream)) return -1;
-    for (int i = 1; i < 3; i++)
-        if (alloc_plane(&pic->plane[i], d.stride_c, d.lines_c, PADH / 2, PADV / 2, c->batch, c->bs_c, c->stream)) return -1;
-    pic->filtered[0] = pic->plane[0];
-    return 0;
+    if (!alloc_planes(c, pic, hpel, lowres)) return 0;
+    x264hip_picture_free(c, pic);                          // what was allocated so far
+    return -1;
 }
+extern "C" int x264hip_picture_alloc(x264hip_frame_ctx *c, x264hip_picture *pic) { return picture_alloc(c, pic, true, true); }
+// A source picture: Y, U, V only (x264_frame_t of an input frame needs no half-pel planes; 3.5 MB per 1080p chain instead of 12.7)
+extern "C" int x264hip_picture_alloc_source(x264hip_frame_ctx *c, x264hip_picture *pic) { return picture_alloc(c, pic, false, false); }
 // A lookahead slot's picture: the source planes and the half-resolution planes (include/x264hip_lookahead.h)
-extern "C" int x264hip_picture_alloc_lookahead(x264hip_frame_ctx *c, x264hip_picture *pic)
-{
-    if (x264hip_picture_alloc_source(c, pic)) return -1;
-    pic->width_lowres = c->width_l; pic->lines_lowres = c->lines_l; pic->stride_lowres = c->stride_l;
-    for (int i = 0; i < 4; i++)
-        if (alloc_plane(&pic->lowres[i], c->stride_l, c->lines_l, PADH, PADV, c->batch, c->bs_l, c->stream)) return -1;
-    return 0;
-}
+extern "C" int x264hip_picture_alloc_lookahead(x264hip_frame_ctx *c, x264hip_picture *pic) { return picture_alloc(c, pic, false, true); }
 // batch element src_b of `src` -> element dst_b of `dst` (Y, U, V with their padding), on the context's stream
 extern "C" int x264hip_picture_copy_element(x264hip_frame_ctx *c, x264hip_picture *dst, int dst_b, const x264hip_picture *src, int src_b)
 {

@@ -1,23 +1,9 @@
 // frame_slice.hip -- host side of the macroblock sweep (x264hip_slice_sweep_frame ...) and the wavefront-schedule kernel variants.
 // The kernel itself lives in slice_kernel.h; its raster-order variant is instantiated in frame_slice_rd.hip (a translation unit of
 // its own so that the two compile side by side).
-#include <mutex>
-#include <unordered_map>
 #include <vector>
 #include "slice_kernel.h"
 #include "x264hip_lookahead.h"
-
-void x264hip_launch_slice_rd(const SwArgs &a, const SwRefs &t, const SwRd &r, hipStream_t stream);
-void x264hip_launch_slice_b(const SwArgs &a, const SwRefs &t, const SwRd &r, hipStream_t stream);
-void x264hip_launch_slice_bt(const SwArgs &a, const SwRefs &t, const SwRd &r, hipStream_t stream);
-void x264hip_launch_slice_rf(const SwArgs &a, const SwRefs &t, const SwRd &r, hipStream_t stream);
-void x264hip_launch_slice_rd_ch(const SwDesc *tab, int n, hipStream_t stream);
-void x264hip_launch_slice_bt_ch(const SwDesc *tab, int n, hipStream_t stream);
-void x264hip_launch_slice_rf_ch(const SwDesc *tab, int n, hipStream_t stream);
-void x264hip_launch_slice_ll(const SwArgs &a, const SwRefs &t, const SwRd &r, hipStream_t stream);
-void x264hip_launch_slice_ll_rf(const SwArgs &a, const SwRefs &t, const SwRd &r, hipStream_t stream);
-void x264hip_launch_slice_ll_ch(const SwDesc *tab, int n, hipStream_t stream);
-void x264hip_launch_slice_ll_rf_ch(const SwDesc *tab, int n, hipStream_t stream);
 
 // b_fast_intra's raster-order term, settled once the frame is complete: macroblocks whose analysis went on without
 // knowing it (it could not change their type) recorded the statistics term for the other answer in cost_alt.
@@ -53,26 +39,16 @@ static const uint8_t k_chroma_qp[52] = {  // i_chroma_qp_table, R/common/macrobl
     0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16, 17, 18, 19, 20, 21, 22, 23, 24, 25, 26, 27, 28, 29,
     29, 30, 31, 32, 32, 33, 34, 34, 35, 35, 36, 36, 37, 37, 37, 38, 38, 38, 39, 39, 39, 39};
 
-extern "C" void x264hip_mb_state_free(x264hip_frame_ctx *c, x264hip_mb_state *st);
-extern "C" int x264hip_mb_state_alloc_ex(x264hip_frame_ctx *c, x264hip_mb_state *st, int flags);
 extern "C" int x264hip_mb_state_alloc(x264hip_frame_ctx *c, x264hip_mb_state *st) { return x264hip_mb_state_alloc_ex(c, st, 0); }
 extern "C" int x264hip_mb_state_alloc_ex(x264hip_frame_ctx *c, x264hip_mb_state *st, int flags)
 {
-    const size_t n = (size_t)c->d.mb_w * c->d.mb_h * c->batch;
-    const bool no_levels = flags & X264HIP_STATE_NO_LEVELS;     // 816 of a macroblock's 1184 bytes: nobody reads them when the sweep writes the payload itself
     memset(st, 0, sizeof(*st));
-    struct { void **p; size_t bytes; } items[] = {
-        {(void **)&st->mb_type, n}, {(void **)&st->partition, n}, {(void **)&st->sub_partition, 4 * n}, {(void **)&st->ref, 4 * n}, {(void **)&st->i4mode, 16 * n},
-        {(void **)&st->i16mode, n}, {(void **)&st->chroma_mode, n}, {(void **)&st->qp, n}, {(void **)&st->t8, n},
-        {(void **)&st->mv, 64 * n}, {(void **)&st->mvr, 4 * SW_MAX_REFS * n}, {(void **)&st->cbp, 2 * n}, {(void **)&st->nnz, 27 * n},
-        {(void **)&st->luma, 512 * n}, {(void **)&st->luma_dc, 32 * n}, {(void **)&st->chroma_dc, 16 * n}, {(void **)&st->chroma_ac, 256 * n},
-        {(void **)&st->cost_intra, 4 * n}, {(void **)&st->cost_inter, 4 * n}, {(void **)&st->cost_intra_alt, 4 * n},
-        {(void **)&st->progress, sizeof(int) * ((size_t)c->d.mb_h * c->batch + 1)}, {(void **)&st->mvd, 64 * n},
-        {(void **)&st->mv1, 64 * n}, {(void **)&st->ref1, 4 * n}, {(void **)&st->mvr1, 4 * n}, {(void **)&st->mvd1, 64 * n}, {(void **)&st->skipbp, n}};
-    for (auto &it : items) {
-        if (no_levels && (it.p == (void **)&st->luma || it.p == (void **)&st->luma_dc || it.p == (void **)&st->chroma_dc || it.p == (void **)&st->chroma_ac)) continue;
-        if (hipMalloc(it.p, it.bytes) != hipSuccess || zero_async(*it.p, it.bytes, c->stream) != 0) {
-            set_error("mb_state_alloc: %zu bytes", it.bytes);
+    for (const StateArray &s : k_state_arrays) {
+        if (s.level && (flags & X264HIP_STATE_NO_LEVELS)) continue;     // nobody reads them when the sweep writes the payload itself
+        const size_t bytes = state_array_bytes(s, c->d.mb_w, c->d.mb_h, c->batch);
+        void **p = state_array(st, s);
+        if (hipMalloc(p, bytes) != hipSuccess || zero_async(*p, bytes, c->stream) != 0) {
+            set_error("mb_state_alloc: %zu bytes", bytes);
             x264hip_mb_state_free(c, st);              // what was allocated so far
             return -1;
         }
@@ -82,10 +58,7 @@ extern "C" int x264hip_mb_state_alloc_ex(x264hip_frame_ctx *c, x264hip_mb_state 
 extern "C" void x264hip_mb_state_free(x264hip_frame_ctx *c, x264hip_mb_state *st)
 {
     (void)c;
-    void *ps[] = {st->mb_type, st->partition, st->sub_partition, st->ref, st->i4mode, st->i16mode, st->chroma_mode, st->qp, st->t8, st->mv, st->mvr, st->cbp,
-                  st->nnz, st->luma, st->luma_dc, st->chroma_dc, st->chroma_ac, st->cost_intra, st->cost_inter, st->cost_intra_alt, st->progress, st->mvd,
-                  st->mv1, st->ref1, st->mvr1, st->mvd1, st->skipbp};
-    for (void *p : ps) if (p) (void)hipFree(p);
+    for (const StateArray &s : k_state_arrays) if (*state_array(st, s)) (void)hipFree(*state_array(st, s));
     memset(st, 0, sizeof(*st));
 }
 
@@ -106,14 +79,20 @@ __global__ __launch_bounds__(128) void k_nr_update(u32 *sum, u32 *count, u16 *of
         offset[cat * 64 + i] = (u16)(((unsigned long long)strength * cnt + sv / 2) / ((unsigned long long)sv * w / 256 + 1));
     }
 }
-extern "C" int x264hip_nr_state_alloc(x264hip_frame_ctx *c, x264hip_nr_state *nr)
+static int nr_alloc_arrays(x264hip_frame_ctx *c, x264hip_nr_state *nr)
 {
-    memset(nr, 0, sizeof(*nr));
     const size_t B = (size_t)c->batch;
     HIPCHK(hipMalloc((void **)&nr->sum, B * 128 * 4)); HIPCHK(hipMalloc((void **)&nr->count, B * 2 * 4)); HIPCHK(hipMalloc((void **)&nr->offset, B * 128 * 2));
     HIPCHK(hipMemsetAsync(nr->sum, 0, B * 128 * 4, c->stream)); HIPCHK(hipMemsetAsync(nr->count, 0, B * 2 * 4, c->stream));
     HIPCHK(hipMemsetAsync(nr->offset, 0, B * 128 * 2, c->stream));
     return 0;
+}
+extern "C" int x264hip_nr_state_alloc(x264hip_frame_ctx *c, x264hip_nr_state *nr)
+{
+    memset(nr, 0, sizeof(*nr));
+    if (!nr_alloc_arrays(c, nr)) return 0;
+    x264hip_nr_state_free(c, nr);                      // what was allocated so far
+    return -1;
 }
 extern "C" void x264hip_nr_state_free(x264hip_frame_ctx *c, x264hip_nr_state *nr)
 {
@@ -131,9 +110,7 @@ extern "C" int x264hip_noise_reduction_update(x264hip_frame_ctx *c, const x264hi
     return 0;
 }
 
-struct ChainAux { hipStream_t stream = nullptr; hipEvent_t ready = nullptr, done = nullptr; };
-// The three argument structures of one sweep launch from the ABI's description of it, and which kernel codes it
-enum { SW_KIND_PLAIN = 0, SW_KIND_RD, SW_KIND_RF, SW_KIND_B, SW_KIND_BT, SW_KIND_LL, SW_KIND_LL_RF, SW_N_KINDS };      // LL: the lossless raster kernels (frame_slice_ll*.hip)
+// The three argument structures of one sweep launch from the ABI's description of it, and which kernel codes it (sweep_tables.h)
 static void sweep_note_frame(const x264hip_slice_params *p, int n_refs, x264hip_mb_state *out);
 static int sweep_build(x264hip_frame_ctx *c, const x264hip_picture *fenc, const x264hip_picture *const *refs, int n_refs,
                        x264hip_picture *recon, const x264hip_slice_params *p, const x264hip_mb_state *l0,
@@ -222,7 +199,7 @@ static int sweep_build(x264hip_frame_ctx *c, const x264hip_picture *fenc, const 
     a.luma = out->luma; a.luma_dc = out->luma_dc; a.chroma_dc = out->chroma_dc; a.chroma_ac = out->chroma_ac;
     a.cost_intra = out->cost_intra; a.cost_inter = out->cost_inter; a.cost_alt = out->cost_intra_alt;
     a.progress = out->progress; a.abort_flag = out->progress + (size_t)c->d.mb_h * c->batch;
-    a.abort_total = (int *)((char *)c->ssd_dev + 24 * (size_t)c->batch + 32);
+    a.abort_total = c->abort_total;
     { const char *e = getenv("X264HIP_SPIN_LIMIT"); a.spin_limit = e && atoi(e) > 0 ? atoi(e) : SW_SPIN_LIMIT; }
     a.prof = (long long *)p->profile;
     a.nr = p->noise_reduction != 0;
@@ -308,21 +285,15 @@ extern "C" int x264hip_slice_sweep_frame(x264hip_frame_ctx *c, const x264hip_pic
     int kind;
     if (sweep_build(c, fenc, refs, n_refs, recon, p, l0, out, a, t, r, kind)) return -1;
     const bool is_p = p->slice_type == 0;
-    HIPCHK(hipMemsetAsync(out->progress, 0, sizeof(int) * ((size_t)c->d.mb_h * c->batch + 1), c->stream));
+    HIPCHK(hipMemsetAsync(out->progress, 0, state_progress_bytes(c->d.mb_h, c->batch), c->stream));
     static int wpe = 0;
     if (!wpe) {                                                      // developer knob: X264HIP_SWEEP_WPE = 1..3
         const char *e = getenv("X264HIP_SWEEP_WPE");
         wpe = e ? atoi(e) : 3;                                       // 3 waves/SIMD (168 VGPRs, 12 waves per CU with 13 KB of LDS each): measured best
         if (wpe < 1 || wpe > 3) wpe = 3;
     }
-    switch (kind) {
-    case SW_KIND_BT: x264hip_launch_slice_bt(a, t, r, c->stream); break;
-    case SW_KIND_B: x264hip_launch_slice_b(a, t, r, c->stream); break;
-    case SW_KIND_RF: x264hip_launch_slice_rf(a, t, r, c->stream); break;
-    case SW_KIND_RD: x264hip_launch_slice_rd(a, t, r, c->stream); break;
-    case SW_KIND_LL: x264hip_launch_slice_ll(a, t, r, c->stream); break;
-    case SW_KIND_LL_RF: x264hip_launch_slice_ll_rf(a, t, r, c->stream); break;
-    default: {
+    if (k_sweep_kinds[kind].frame) k_sweep_kinds[kind].frame(a, t, r, c->stream);
+    else {
         const dim3 grid((unsigned)(a.batch_pad * a.mb_h)), block(64);
         switch (a.lossless ? 0 : wpe) {
         case 0: hipLaunchKernelGGL((k_slice_sweep<2, true>), grid, block, 0, c->stream, a, t, r, nullptr); break;
@@ -330,7 +301,6 @@ extern "C" int x264hip_slice_sweep_frame(x264hip_frame_ctx *c, const x264hip_pic
         case 3: hipLaunchKernelGGL(k_slice_sweep<3>, grid, block, 0, c->stream, a, t, r, nullptr); break;
         default: hipLaunchKernelGGL(k_slice_sweep<2>, grid, block, 0, c->stream, a, t, r, nullptr); break;
         }
-    }
     }
     if (kind == SW_KIND_PLAIN && is_p && a.flags_intra)
         hipLaunchKernelGGL(k_resolve_fast_intra, dim3(c->batch), dim3(64), 0, c->stream, (const signed char *)out->mb_type, out->cost_intra,
@@ -342,19 +312,23 @@ extern "C" int x264hip_slice_sweep_frame(x264hip_frame_ctx *c, const x264hip_pic
 
 // The chain-table launch: every entry is a sweep of ONE chain (batch element) with its own pictures, states and slice parameters.
 static int sweep_chains(x264hip_frame_ctx *c, x264hip_chain_sweep *e, int n, void *staging_host, void *table_dev, void *ev_ip, void *ev_b, bool join);
-static std::mutex g_aux_mu;
-static std::unordered_map<x264hip_frame_ctx *, ChainAux> g_aux_of;
-// the stream the B kernel of this context's chain-table launches runs on (default: one the library creates): e.g. one restricted to
-// a part of the device (x264hip_stream_create_cu_range) while the context's own stream has the rest
+static int b_events(x264hip_frame_ctx *c)
+{
+    if (c->b_ready) return 0;
+    HIPCHK(hipEventCreateWithFlags(&c->b_ready, hipEventDisableTiming));
+    HIPCHK(hipEventCreateWithFlags(&c->b_done, hipEventDisableTiming));
+    return 0;
+}
+// the stream the B kernel of this context's chain-table launches runs on: e.g. one restricted to a part of the device
+// (x264hip_stream_create_cu_range) while the context's own stream has the rest.  It stays the caller's, who destroys it after the
+// context or after handing the context another.  NULL: back to the default, a stream the library creates (and owns) when a launch needs it.
 extern "C" int x264hip_frame_ctx_set_b_stream(x264hip_frame_ctx *c, void *hip_stream)
 {
-    std::lock_guard<std::mutex> g(g_aux_mu);
-    ChainAux &ax = g_aux_of[c];
-    if (!ax.ready) {
-        HIPCHK(hipEventCreateWithFlags(&ax.ready, hipEventDisableTiming));
-        HIPCHK(hipEventCreateWithFlags(&ax.done, hipEventDisableTiming));
+    if (b_events(c)) return -1;
+    if (hip_stream || !c->own_b_stream) {
+        if (c->own_b_stream) (void)hipStreamDestroy(c->b_stream);
+        c->b_stream = (hipStream_t)hip_stream; c->own_b_stream = false;
     }
-    ax.stream = (hipStream_t)hip_stream;
     return 0;
 }
 extern "C" int x264hip_slice_sweep_chains(x264hip_frame_ctx *c, x264hip_chain_sweep *e, int n, void *staging_host, void *table_dev)
@@ -375,7 +349,7 @@ static int sweep_chains(x264hip_frame_ctx *c, x264hip_chain_sweep *e, int n, voi
     if (n <= 0) return 0;
     if (!staging_host || !table_dev) { set_error("slice_sweep_chains: staging / table buffers missing"); return -1; }
     SwDesc *st = (SwDesc *)staging_host;
-    // entries sorted by kernel: [RD | RF | BT], or [LL | LL_RF] when the launch is lossless; a first pass builds, a second places
+    // entries sorted by kind (sweep_tables.h): a first pass builds, a second places
     int cnt[SW_N_KINDS] = {0};
     static thread_local std::vector<SwDesc> tmp;
     static thread_local std::vector<int> kinds;
@@ -386,7 +360,7 @@ static int sweep_chains(x264hip_frame_ctx *c, x264hip_chain_sweep *e, int n, voi
         if (!s.params || !s.params->rd || !s.params->rd->write) { set_error("slice_sweep_chains: entry %d: the chain table belongs to the raster variant with the entropy coder in the loop (params.rd, write = 1)", i); return -1; }
         int kind;
         if (sweep_build(c, s.fenc, s.refs, s.n_refs, s.recon, s.params, s.l0, s.out, tmp[i].a, tmp[i].t, tmp[i].r, kind)) return -1;
-        if (kind == SW_KIND_B) kind = SW_KIND_BT;                       // one B kernel in the table launches
+        kind = k_sweep_kinds[kind].in_table;
         tmp[i].a.chain = s.chain;
         kinds[i] = kind; cnt[kind]++;
         sweep_note_frame(s.params, s.n_refs, s.out);
@@ -395,40 +369,29 @@ static int sweep_chains(x264hip_frame_ctx *c, x264hip_chain_sweep *e, int n, voi
     // SAD lookahead), so a table that mixes the two is a caller's mistake, not a schedule
     const int n_ll = cnt[SW_KIND_LL] + cnt[SW_KIND_LL_RF];
     if (n_ll && n_ll != n) { set_error("slice_sweep_chains: %d of %d entries are lossless (QP 0): a chain table is all-lossless or not at all", n_ll, n); return -1; }
-    int base[SW_N_KINDS] = {0}, at[SW_N_KINDS];
-    base[SW_KIND_RD] = 0; base[SW_KIND_RF] = cnt[SW_KIND_RD]; base[SW_KIND_BT] = base[SW_KIND_RF] + cnt[SW_KIND_RF];
-    base[SW_KIND_LL] = 0; base[SW_KIND_LL_RF] = cnt[SW_KIND_LL];
-    for (int k = 0; k < SW_N_KINDS; k++) at[k] = base[k];
+    int base[SW_N_KINDS], at[SW_N_KINDS];
+    sweep_place(cnt, base);
+    memcpy(at, base, sizeof(at));
     for (int i = 0; i < n; i++) st[at[kinds[i]]++] = tmp[i];
     HIPCHK(hipMemcpyAsync(table_dev, st, sizeof(SwDesc) * (size_t)n, hipMemcpyHostToDevice, c->stream));
     const SwDesc *tab = (const SwDesc *)table_dev;
     // The I / P chains and the B chains of a step are different chains: their kernels run side by side, the B kernel on a stream of its
     // own between two events (behind the table's upload, ahead of whatever follows on the context's stream).
     const bool two = cnt[SW_KIND_BT] && (cnt[SW_KIND_RD] || cnt[SW_KIND_RF] || !join);
-    ChainAux *ax = nullptr;
     if (two) {
-        std::lock_guard<std::mutex> g(g_aux_mu);
-        ax = &g_aux_of[c];
-        if (!ax->stream) HIPCHK(hipStreamCreateWithFlags(&ax->stream, hipStreamNonBlocking));
-        if (!ax->ready) {
-            HIPCHK(hipEventCreateWithFlags(&ax->ready, hipEventDisableTiming));
-            HIPCHK(hipEventCreateWithFlags(&ax->done, hipEventDisableTiming));
-        }
-        HIPCHK(hipEventRecord(ax->ready, c->stream));
-        HIPCHK(hipStreamWaitEvent(ax->stream, ax->ready, 0));
+        if (!c->b_stream) { HIPCHK(hipStreamCreateWithFlags(&c->b_stream, hipStreamNonBlocking)); c->own_b_stream = true; }
+        if (b_events(c)) return -1;
+        HIPCHK(hipEventRecord(c->b_ready, c->stream));
+        HIPCHK(hipStreamWaitEvent(c->b_stream, c->b_ready, 0));
     }
-    // the I / P kernel first: its wavefronts -- the step's long ones -- are dealt evenly over the SIMDs before the B kernel's fill the rest
-    if (cnt[SW_KIND_RD]) x264hip_launch_slice_rd_ch(tab + base[SW_KIND_RD], cnt[SW_KIND_RD], c->stream);
-    if (cnt[SW_KIND_RF]) x264hip_launch_slice_rf_ch(tab + base[SW_KIND_RF], cnt[SW_KIND_RF], c->stream);
-    if (cnt[SW_KIND_LL]) x264hip_launch_slice_ll_ch(tab + base[SW_KIND_LL], cnt[SW_KIND_LL], c->stream);
-    if (cnt[SW_KIND_LL_RF]) x264hip_launch_slice_ll_rf_ch(tab + base[SW_KIND_LL_RF], cnt[SW_KIND_LL_RF], c->stream);
-    if (cnt[SW_KIND_BT]) x264hip_launch_slice_bt_ch(tab + base[SW_KIND_BT], cnt[SW_KIND_BT], two ? ax->stream : c->stream);
+    const hipStream_t b_stream = two ? c->b_stream : c->stream;
+    sweep_enqueue(tab, cnt, base, c->stream, b_stream);
     if (two && join) {
-        HIPCHK(hipEventRecord(ax->done, ax->stream));
-        HIPCHK(hipStreamWaitEvent(c->stream, ax->done, 0));
+        HIPCHK(hipEventRecord(c->b_done, c->b_stream));
+        HIPCHK(hipStreamWaitEvent(c->stream, c->b_done, 0));
     }
     if (ev_ip) HIPCHK(hipEventRecord((hipEvent_t)ev_ip, c->stream));
-    if (ev_b) HIPCHK(hipEventRecord((hipEvent_t)ev_b, two ? ax->stream : c->stream));
+    if (ev_b) HIPCHK(hipEventRecord((hipEvent_t)ev_b, b_stream));
     HIPCHK(hipGetLastError());
     return 0;
 }
@@ -436,7 +399,7 @@ extern "C" size_t x264hip_chain_sweep_bytes(void) { return sizeof(SwDesc); }
 // the abort flag of a state (what x264hip_slice_sweep_frame clears before each launch; a chain-table caller clears it once per state it writes)
 extern "C" int x264hip_mb_state_clear_progress(x264hip_frame_ctx *c, x264hip_mb_state *st)
 {
-    HIPCHK(hipMemsetAsync(st->progress, 0, sizeof(int) * ((size_t)c->d.mb_h * c->batch + 1), c->stream));
+    HIPCHK(hipMemsetAsync(st->progress, 0, state_progress_bytes(c->d.mb_h, c->batch), c->stream));
     return 0;
 }
 
@@ -445,7 +408,7 @@ extern "C" int x264hip_slice_sweep_status(x264hip_frame_ctx *c, const x264hip_mb
     int flag = 0, total = 0;
     HIPCHK(hipStreamSynchronize(c->stream));
     HIPCHK(hipMemcpy(&flag, st->progress + (size_t)c->d.mb_h * c->batch, sizeof(int), hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(&total, (char *)c->ssd_dev + 24 * (size_t)c->batch + 32, sizeof(int), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(&total, c->abort_total, sizeof(int), hipMemcpyDeviceToHost));
     if (flag) { set_error("slice_sweep: a wavefront gave up -- waiting for its neighbours, or out of payload space (aborted frame)"); return -1; }
     // sticky: an aborted frame may have been used as a reference since, and its own flag is cleared when its state is reused
     if (total) { set_error("slice_sweep: %d wavefront(s) of an EARLIER frame of this context gave up -- waiting, or out of payload space (aborted frame): everything coded since is invalid", total); return -1; }

@@ -1331,3 +1331,6 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(RF ? 1 : 2))
     constexpr bool LL = true, RD = true, BS = false, TD = false;
 #include "slice_sweep_body.h"
 }
+
+// the launch functions of the instantiation files (frame_slice_*.hip) and the table of kinds the host side walks
+#include "sweep_tables.h"
