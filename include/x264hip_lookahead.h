@@ -19,8 +19,9 @@ int x264hip_picture_alloc_lookahead(x264hip_frame_ctx *c, x264hip_picture *pic);
  * chain's sweep, described exactly like a call of x264hip_slice_sweep_frame -- its own source picture, references, reconstruction,
  * states and slice parameters (QP, POCs, lowres vectors, list 1) -- and the chain (batch element) it applies to: the pictures and states
  * are the batch-wide ones, the entry touches element `chain` of each.  One launch per kernel kind (I / P, I / P with the subme 8-9
- * refinement, B), each block taking its arguments from its entry (csrc/slice_kernel.h, template argument CH).  The raster variant with
- * the entropy coder in the loop only (params->rd with write = 1).  Every entry's `out` state gets the frame-level scalars later frames
+ * refinement, B), each block taking its arguments from its entry (csrc/slice_kernel.h, template argument CH).  The raster variant only
+ * (params->rd): with the CABAC coder in the loop (write = 1) in every entry, or in none -- an all-CAVLC table (cabac = 0, write = 0, states
+ * with level arrays), whose slices x264hip_cavlc_write_chains writes afterwards; a table that mixes the two is refused.  Every entry's `out` state gets the frame-level scalars later frames
  * read (poc, ref_poc ...): give each chain its own COPY of the x264hip_mb_state structure (same device arrays, its own scalars).  The
  * abort flag of every distinct state written must be cleared before the call (x264hip_mb_state_clear_progress).  staging_host (pinned)
  * and table_dev: n * x264hip_chain_sweep_bytes() each, left alone until the stream has passed the call. */
@@ -60,14 +61,17 @@ int x264hip_frame_ctx_elements(x264hip_frame_ctx *c, const int *elems_dev, int n
 
 
 /* The CAVLC writer: x264_macroblock_write_cavlc + x264_slice_write's skip runs (R/encoder/cavlc.c:60-620, R/encoder/encoder.c:1200-1280) for
- * every chain's I or P slice, as a pass over the state x264hip_slice_sweep_frame left (a `--no-cabac` slice below the RD levels: the wavefront
- * variant at constant QP, or the raster variant without its writer when adaptive quantisation gives every macroblock its QP; decisions and
- * coefficient levels in the x264hip_mb_state -- allocate it WITH level arrays).  payload: device
+ * every chain's I, P or B slice, as a pass over the state x264hip_slice_sweep_frame left (a `--no-cabac` slice below the RD levels: the wavefront
+ * variant at constant QP, or the raster variant without its writer -- rd.write = 0 -- when adaptive quantisation gives every macroblock its QP
+ * or the slice is a B slice; decisions and coefficient levels in the x264hip_mb_state -- allocate it WITH level arrays; a B slice also reads
+ * the state's list-1 arrays ref1 / mv1).  payload: device
  * [batch][payload_cap] bytes, chain b's slice_data() starts X264HIP_PAYLOAD_LEAD (64) bytes into its slot, from bit 0, rbsp trailing bits
  * included; payload_len: device [batch] int32; mb_bits (optional): device [batch][n_mb], bit position after every macroblock.
- * Asynchronous on the context's stream.  I_PCM macroblocks and a slot too small end with x264hip_slice_sweep_status reporting an abort. */
+ * Asynchronous on the context's stream.  I_PCM macroblocks and a slot too small end with x264hip_slice_sweep_status reporting an abort:
+ * an I or P slice of x264hip_cavlc_write_frame stops 1024 bytes before its slot's end (payload_cap >= 4096), a B slice and every slice of
+ * x264hip_cavlc_write_chains before a macroblock whose worst case (2624 bytes, derived in csrc/frame_cavlc.hip) might not fit. */
 typedef struct {
-    int slice_type;            /* 0 P, 2 I */
+    int slice_type;            /* 0 P, 1 B, 2 I */
     int n_ref0;                /* h->mb.pic.i_fref[0]: references of list 0 (the number te() is written against) */
     int analyse_inter;         /* param.analyse.inter (X264_ANALYSE_PSUB8x8 decides how sub-partition types are written) */
     int transform8x8;          /* pps->b_transform_8x8_mode */
@@ -76,6 +80,21 @@ typedef struct {
     int slice_qp;              /* h->sh.i_qp: what mb_qp_delta of the first coded macroblock is relative to (per-macroblock QPs: the state's qp array) */
 } x264hip_cavlc_params;
 int x264hip_cavlc_write_frame(x264hip_frame_ctx *c, const x264hip_mb_state *st, const x264hip_cavlc_params *p);
+
+/* The writer for chains that do not move in lock step: the counterpart of x264hip_slice_sweep_chains for an all-CAVLC chain table (every
+ * entry of the sweep's table with cabac = 0 and rd.write = 0).  Every entry is ONE chain's slice: the chain (batch element), the state its
+ * sweep wrote (that chain's copy of the x264hip_mb_state) and the slice's x264hip_cavlc_params -- slice type, n_ref0, slice QP and the
+ * batch-wide payload / payload_len / mb_bits buffers, of which the entry writes element `chain` (its payload slot).  One launch writes all
+ * entries, I, P and B slices side by side, one wavefront each; asynchronous on the context's stream, so behind a sweep enqueued before it.
+ * staging_host (pinned) and table_dev: n * x264hip_chain_cavlc_bytes() each, left alone until the stream has passed the call.
+ * payload_cap is at least X264HIP_PAYLOAD_LEAD + 2624. */
+typedef struct {
+    int chain;
+    const x264hip_mb_state *state;
+    const x264hip_cavlc_params *params;
+} x264hip_chain_cavlc;
+int x264hip_cavlc_write_chains(x264hip_frame_ctx *c, const x264hip_chain_cavlc *entries, int n, void *staging_host, void *table_dev);
+size_t x264hip_chain_cavlc_bytes(void);
 
 #ifdef __cplusplus
 }

@@ -123,7 +123,10 @@ static int sweep_build(x264hip_frame_ctx *c, const x264hip_picture *fenc, const 
     if (is_b) {
         if (!pb || !pb->fref1 || !pb->l1_state || !p->rd) { set_error("slice_sweep: a B slice needs x264hip_slice_params.b (list 1) and .rd (the raster variant)"); return -1; }
         if ((!pb->direct_spatial || pb->direct_score) && !p->rd->stale) { set_error("slice_sweep: temporal direct prediction needs x264hip_slice_rd.stale (in every sweep of the chain)"); return -1; }
-        if (p->subme < 2 || p->subme > 8 || !p->rd->write || !p->cabac) { set_error("slice_sweep: B slices are built for subme 2..8 with the CABAC writer in the loop (subme 9 refines a B macroblock's vectors by RD: x264_me_refine_bidir_rd, not built)"); return -1; }
+        // a CAVLC B slice: the same kernels without their writer (the analysis below the RD levels never asks which entropy coder follows);
+        // x264hip_cavlc_write_frame / _chains write it from the state
+        const bool b_cavlc = !p->cabac && !p->rd->write && p->subme <= 5;
+        if (p->subme < 2 || p->subme > 8 || (!b_cavlc && (!p->rd->write || !p->cabac))) { set_error("slice_sweep: B slices are built for subme 2..8 with the CABAC writer in the loop, and for subme 2..5 without a writer (cabac = 0, rd.write = 0: a CAVLC slice, written from the state afterwards); subme 9 refines a B macroblock's vectors by RD: x264_me_refine_bidir_rd, not built"); return -1; }
         if (p->noise_reduction || p->lossless) { set_error("slice_sweep: B slices with --nr / lossless are not built"); return -1; }
         if (!out->mv1 || !pb->l1_state->mb_type) { set_error("slice_sweep: mb_state without list-1 arrays"); return -1; }
     }
@@ -350,14 +353,15 @@ static int sweep_chains(x264hip_frame_ctx *c, x264hip_chain_sweep *e, int n, voi
     if (!staging_host || !table_dev) { set_error("slice_sweep_chains: staging / table buffers missing"); return -1; }
     SwDesc *st = (SwDesc *)staging_host;
     // entries sorted by kind (sweep_tables.h): a first pass builds, a second places
-    int cnt[SW_N_KINDS] = {0};
+    int cnt[SW_N_KINDS] = {0}, n_cavlc = 0;
     static thread_local std::vector<SwDesc> tmp;
     static thread_local std::vector<int> kinds;
     tmp.resize((size_t)n); kinds.resize((size_t)n);
     for (int i = 0; i < n; i++) {
         x264hip_chain_sweep &s = e[i];
         if (s.chain < 0 || s.chain >= c->batch) { set_error("slice_sweep_chains: entry %d: chain %d", i, s.chain); return -1; }
-        if (!s.params || !s.params->rd || !s.params->rd->write) { set_error("slice_sweep_chains: entry %d: the chain table belongs to the raster variant with the entropy coder in the loop (params.rd, write = 1)", i); return -1; }
+        if (!s.params || !s.params->rd || (!s.params->rd->write && s.params->cabac)) { set_error("slice_sweep_chains: entry %d: the chain table belongs to the raster variant (params.rd) with the CABAC coder in the loop (write = 1), or without a writer for a CAVLC slice (cabac = 0, write = 0)", i); return -1; }
+        n_cavlc += !s.params->rd->write;
         int kind;
         if (sweep_build(c, s.fenc, s.refs, s.n_refs, s.recon, s.params, s.l0, s.out, tmp[i].a, tmp[i].t, tmp[i].r, kind)) return -1;
         kind = k_sweep_kinds[kind].in_table;
@@ -369,6 +373,9 @@ static int sweep_chains(x264hip_frame_ctx *c, x264hip_chain_sweep *e, int n, voi
     // SAD lookahead), so a table that mixes the two is a caller's mistake, not a schedule
     const int n_ll = cnt[SW_KIND_LL] + cnt[SW_KIND_LL_RF];
     if (n_ll && n_ll != n) { set_error("slice_sweep_chains: %d of %d entries are lossless (QP 0): a chain table is all-lossless or not at all", n_ll, n); return -1; }
+    // ... and all-CAVLC or not at all: the caller follows the launch with ONE x264hip_cavlc_write_chains over the same chains, and a CABAC
+    // chain's payload slot already holds its slice then
+    if (n_cavlc && n_cavlc != n) { set_error("slice_sweep_chains: %d of %d entries are CAVLC slices without a writer (cabac = 0, rd.write = 0): a chain table is all-CAVLC or not at all", n_cavlc, n); return -1; }
     int base[SW_N_KINDS], at[SW_N_KINDS];
     sweep_place(cnt, base);
     memcpy(at, base, sizeof(at));

@@ -2,6 +2,7 @@
 
     python -m x264_vs2008_amd.encode --crf 23 --ref 3 --bframes 3 --b-adapt 1 --subme 7 --8x8dct --trellis 1 --weightb --mixed-refs -o out.264 in.y4m
     python -m x264_vs2008_amd.encode --qp 26 --no-cabac --me dia --subme 0 --partitions none --no-deblock --scenecut -1 -o out.264 in.yuv 352x288
+    python -m x264_vs2008_amd.encode --crf 23 --no-cabac --subme 5 --bframes 2 -o out.264 in.y4m      # CAVLC through the frame queue: CRF, B frames, scene cuts
     python -m x264_vs2008_amd.encode [options] -o out_%d.264 a.y4m b.y4m c.y4m        # one stream per input, coded side by side (same size and options)
     python -m x264_vs2008_amd.encode --qp 0 -o out.264 in.y4m                         # lossless (High 4:4:4 Predictive SPS): what x264_validate_parameters
                                                                                       # turns off at QP 0 is off here too, the lookahead scores with SAD
@@ -18,7 +19,7 @@ given at once are coded as chains of one batch.
 
 Readers: raw I420 (R/muxers.c:63-122: frame i at i * w * h * 3 / 2) and YUV4MPEG2 (:124-316: W, H, F from the stream header, C420* only, every
 FRAME header skipped to its newline).  Refused, never approximated: what the library refuses (x264hip_validate_parameters, the encoders' own
-checks) -- ABR / VBV / 2-pass, --direct none, B frames or adaptive decisions with --no-cabac, interlaced, threads > 1, b-pyramid.
+checks) -- ABR / VBV / 2-pass, --direct none, --no-cabac with --subme 6 and above (the RD levels), interlaced, threads > 1, b-pyramid.
 Scene cuts work as in the reference: by default after the fact (a P picture that should have been intra is coded again, encoder.c:1603-1699), with
 --pre-scenecut in the lookahead."""
 import argparse
@@ -209,8 +210,18 @@ def needs_lookahead(p):
     return bool(p.bframe or p.rc_method == mux.RC_CRF or (p.scenecut_threshold >= 0 and p.keyint_max > 1))
 
 
+def check_built(p):
+    """What the validated parameters p ask for that no encoder here builds, said before anything is allocated.  x264_validate_parameters has
+    already done what the reference does for !b_cabac (trellis off); CAVLC slices -- I, P and B, constant QP or CRF, with or without scene
+    cuts -- are coded below the RD levels only."""
+    if not p.cabac and p.subpel_refine >= 6:
+        raise ValueError("--no-cabac with --subme %d: the RD levels price CAVLC bits with a counting twin of the writer, which is not built "
+                         "(--subme 5 and below are)" % p.subpel_refine)
+
+
 def encode_streams(lib, p, sources, n_frames, sinks):
     """p: validated parameters (mux.encoder_params); sources: readers of equal picture size; sinks: binary files, one per source."""
+    check_built(p)
     from .frame import JVT_LISTS, cqm_init
     from . import slice as sl
     B, w, h = len(sources), p.width, p.height
@@ -242,9 +253,6 @@ def encode_streams(lib, p, sources, n_frames, sinks):
         finally:
             enc.close()
         return coded
-    if not p.cabac:
-        raise ValueError("--no-cabac with B frames, CRF or a scene cut: the frame queue's encoder (StreamEncoder) codes CABAC slices; CAVLC streams are the "
-                         "constant-QP I / P ones (--qp N --bframes 0 --scenecut -1)")
     from .stream import StreamEncoder
     enc = StreamEncoder(lib, w, h, cq, batch=B, n_frames=n_frames, crf=p.rf_constant if p.rc_method == mux.RC_CRF else None, b_adapt=p.bframe_adaptive,
                         bframe_bias=p.bframe_bias, keyint_min=p.keyint_min, scenecut_threshold=p.scenecut_threshold, pre_scenecut=p.pre_scenecut,

@@ -25,7 +25,7 @@ class Cfg(C.Structure):
 RESTYPES = {
     C.c_char_p: ("x264hip_last_error",),
     C.c_float: ("x264hip_event_elapsed_ms",),
-    C.c_size_t: ("x264hip_lookahead_state_bytes", "x264hip_lookahead_task_bytes", "x264hip_chain_sweep_bytes"),
+    C.c_size_t: ("x264hip_lookahead_state_bytes", "x264hip_lookahead_task_bytes", "x264hip_chain_sweep_bytes", "x264hip_chain_cavlc_bytes"),
     C.c_void_p: ("x264hip_malloc", "x264hip_host_alloc", "x264hip_stream_create", "x264hip_stream_create_high_priority",
                  "x264hip_stream_create_cu_range", "x264hip_event_create", "x264hip_frame_ctx_new", "x264hip_frame_ctx_stream",
                  "x264hip_lookahead_new"),

@@ -50,6 +50,11 @@ class CavlcParams(C.Structure):
                 ("payload", C.c_void_p), ("payload_cap", C.c_int), ("payload_len", C.c_void_p), ("mb_bits", C.c_void_p), ("slice_qp", C.c_int)]
 
 
+class ChainCavlc(C.Structure):
+    """x264hip_chain_cavlc: one chain's slice in a launch of x264hip_cavlc_write_chains"""
+    _fields_ = [("chain", C.c_int), ("state", C.c_void_p), ("params", C.c_void_p)]
+
+
 PAYLOAD_LEAD = 64
 MB_BYTES_MAX = 8192          # SW_MB_BYTES_MAX (csrc/slice_kernel.h): the sweep stops before a macroblock whose worst case might not fit
 MB_BYTES_AVG = 800           # what the default payload buffer provides per macroblock
@@ -149,9 +154,10 @@ class ChainEncoder:
         # the raster-order variant of the sweep: needed by the RD levels, trellis, adaptive quantisation, or simply to get the payload
         # a CAVLC slice's payload is written by a pass over the state the sweep leaves (x264hip_cavlc_write_frame): CAVLC has no adaptive
         # state, so it needs no place in the macroblock loop and the wavefront variant stays the one that codes such slices (with adaptive
-        # quantisation: the raster variant without its writer, whose QP rules leave every macroblock's final QP in the state)
-        self.cavlc = bool(write and not cabac and subme < 6 and not trellis and not bframes)
-        self.raster = bool(subme >= 6 or trellis or aq_mode or (write and not self.cavlc)) if raster is None else bool(raster)
+        # quantisation, and with B frames, which only the raster variant codes: the raster variant without its writer, whose QP rules leave
+        # every macroblock's final QP in the state)
+        self.cavlc = bool(write and not cabac and subme < 6 and not trellis)
+        self.raster = bool(subme >= 6 or trellis or aq_mode or (write and not self.cavlc) or (self.cavlc and bframes)) if raster is None else bool(raster)
         self.rd_opt = dict(trellis=trellis, aq_mode=aq_mode, aq_strength=aq_strength, write=int(bool((write and not self.cavlc) or subme >= 6 or trellis)),
                            cabac_init_idc=cabac_init_idc, qp_min=qp_min, qp_max=qp_max)
         self.ctx = FrameCtx(lib, width, height, batch=batch)
@@ -377,7 +383,7 @@ class ChainEncoder:
             L.x264hip_event_record(C.c_void_p(ev[1]), C.c_void_p(c.stream))
             self.events.append((ev[0], ev[1], stype, len(refs) + len(refs1)))
         if self.cavlc:                                 # x264_macroblock_write_cavlc for every macroblock of every chain, from the state just written
-            rb = self.rd_bufs
+            rb = self.last_bufs if self.raster else self.rd_bufs       # (a B frame on a lane: the lane's payload buffers)
             cp = CavlcParams(slice_type=stype, n_ref0=len(refs), analyse_inter=o["inter"], transform8x8=o["transform8x8"], cqm_custom=0,
                              payload=rb["payload"].ptr, payload_cap=self.payload_cap, payload_len=rb["payload_len"].ptr, mb_bits=rb["mb_bits"].ptr,
                              slice_qp=qp)

@@ -21,7 +21,7 @@ import numpy as np
 
 from . import lookahead as LA
 from .frame import DeviceArray
-from .slice import COST_SPAN, ChainEncoder, MbState, SLICE_B, SLICE_I, SLICE_P, SliceB
+from .slice import COST_SPAN, CavlcParams, ChainCavlc, ChainEncoder, MbState, SLICE_B, SLICE_I, SLICE_P, SliceB
 
 
 class ChainSweep(C.Structure):
@@ -42,13 +42,21 @@ class StreamEncoder(ChainEncoder):
     def __init__(self, lib, width, height, cqm, batch=1, crf=None, b_adapt=1, bframe_bias=0, keyint_min=0, scenecut_threshold=40, pre_scenecut=1,
                  ip_factor=1.4, pb_factor=1.3, qcompress=0.6, qp_step=4, n_slots=0, speculative=True, limits=None, n_frames=None, lookahead_priority=False, b_cus=0, **kw):
         kw.setdefault("write", 1)
+        if not kw.get("cabac", 0):
+            # --no-cabac: the chain-table raster kernels without their writer leave decisions and levels in the states, one launch of
+            # x264hip_cavlc_write_chains behind them writes every chain's slice.  Rate control and the post-encode scene cut read the states.
+            if kw.get("subme", 0) >= 6:
+                raise ValueError("StreamEncoder: cabac=0 with subme >= 6 (the RD levels price CAVLC bits with a counting twin of the writer: not built)")
+            kw["trellis"] = 0                          # x264_validate_parameters: trellis needs CABAC
+            kw.setdefault("levels", True)
+            kw["raster"] = True
         kw.setdefault("levels", False)
         if kw.get("lanes"):
             raise ValueError("StreamEncoder: the chains of a step already run side by side; lanes belong to the lock-step encoder")
         self._direct_auto_ok = True                     # --direct auto: the running scores live here (c_dscore)
         super().__init__(lib, width, height, cqm, batch=batch, **kw)
-        if not self.raster or not self.rd_opt["write"]:
-            raise ValueError("StreamEncoder: the chain-table sweep is the raster variant with the entropy coder in the loop")
+        if not self.raster or not (self.rd_opt["write"] or self.cavlc):
+            raise ValueError("StreamEncoder: the chain-table sweep is the raster variant with the entropy coder in the loop, or followed by the CAVLC pass")
         o, d = self.opt, self.ctx.dims
         if self.lossless:              # x264_validate_parameters (R/encoder/encoder.c:401-417): constant QP 0 for every frame type, no B frames
             crf, ip_factor, pb_factor = None, 1.0, 1.0
@@ -104,6 +112,11 @@ class StreamEncoder(ChainEncoder):
         self.tab_host = lib.x264hip_host_alloc(C.c_size_t(tb * B))
         self.tab_dev = DeviceArray(lib, (tb * B,), np.uint8)
         self.elems_dev = [DeviceArray(lib, (B,), np.int32) for _ in range(len(self.pool))]
+        self.cv_host, self.cv_dev, self._cv = None, None, []       # the table of x264hip_cavlc_write_chains; what _entry notes for it
+        if self.cavlc:
+            cvb = lib.x264hip_chain_cavlc_bytes()
+            self.cv_host = lib.x264hip_host_alloc(C.c_size_t(cvb * B))
+            self.cv_dev = DeviceArray(lib, (cvb * B,), np.uint8)
         self.flushing = False
         self.coded_now = [None] * B
         self.n_sweeps = 0
@@ -267,6 +280,7 @@ class StreamEncoder(ChainEncoder):
         the two timing events around the launch if self.sweep_events collects them."""
         L = self.lib
         keep, written, filt, out = [], set(), {}, []
+        self._cv = []
         entries = (ChainSweep * len(pairs))()
         for k, (ci, fr) in enumerate(pairs):
             entries[k], cd, pic_i = self._entry(ci, fr, keep)
@@ -288,6 +302,11 @@ class StreamEncoder(ChainEncoder):
             c.check(L.x264hip_slice_sweep_chains(c.h, entries, len(pairs), tab_host, tab_dev), "slice_sweep_chains")
         if ev:
             L.x264hip_event_record(C.c_void_p(ev[1]), C.c_void_p(c.stream))
+        if self.cavlc:                                     # every chain's slice from the state its sweep just wrote: I, P and B chains in one launch
+            cv = (ChainCavlc * len(self._cv))()
+            for k, (ci, mine, cp) in enumerate(self._cv):
+                cv[k] = ChainCavlc(ci, C.addressof(mine), C.addressof(cp))
+            c.check(L.x264hip_cavlc_write_chains(c.h, cv, len(self._cv), C.c_void_p(self.cv_host), self.cv_dev.p), "cavlc_write_chains")
         if self.nr:                                        # x264_noise_reduction_update at the end of every frame (encoder.c:1755)
             c.check(L.x264hip_noise_reduction_update(c.h, C.byref(self.nr), self.opt["noise_reduction"]), "noise_reduction_update")
         for pic_i, chains in filt.items():
@@ -344,7 +363,7 @@ class StreamEncoder(ChainEncoder):
             lw1 = self.look.mv_ptr(ci, fr.frame, 1, fr.ref1_frame - fr.frame) - 4 * n * ci
         # (cost_mv: a row of the table of all QPs: no allocation while kernels run -- hipMalloc waits for the device)
         p = self.slice_params(stype, qp, poc, rb["cost_mv_all"].ptr + qp * (2 * COST_SPAN + 1) * 2, lw0)
-        rd = self.slice_rd(rb, fr.f_qpm, self.c_coded[ci], self.aq_slots[slot][1].ptr if self.aq_slots else None, 1, 0)
+        rd = self.slice_rd(rb, fr.f_qpm, self.c_coded[ci], self.aq_slots[slot][1].ptr if self.aq_slots else None, 0 if self.cavlc else 1, 0)
         p.rd = C.addressof(rd)
         keep += [p, rd]
         dsp = self.bopt["direct_spatial"]
@@ -362,6 +381,12 @@ class StreamEncoder(ChainEncoder):
         arr = (C.c_void_p * max(len(refs), 1))(*[C.addressof(r[0]) for r in refs]) if refs else None
         mine = MbState.from_buffer_copy(state.st)        # this chain's view of the state: the device arrays + its own frame-level scalars
         keep += [arr, mine]
+        if self.cavlc:
+            cp = CavlcParams(slice_type=stype, n_ref0=len(refs), analyse_inter=self.opt["inter"], transform8x8=self.opt["transform8x8"], cqm_custom=0,
+                             payload=rb["payload"].ptr, payload_cap=self.payload_cap, payload_len=rb["payload_len"].ptr, mb_bits=rb["mb_bits"].ptr,
+                             slice_qp=qp)
+            keep.append(cp)
+            self._cv.append((ci, mine, cp))
         entry = ChainSweep(ci, C.addressof(self.look.pics[slot]), C.cast(arr, C.c_void_p) if arr else None, len(refs), C.addressof(recon),
                                 C.addressof(p), C.addressof(refs[0][1]) if refs else None, C.addressof(mine))
         cd = Coded()
@@ -405,8 +430,11 @@ class StreamEncoder(ChainEncoder):
         for pair in self.aq_slots or []:
             for a in pair:
                 a.free()
-        for a in [self.tab_dev] + self.elems_dev + (self.stats_dev or []) + ([self.dscore_dev] if self.dscore_dev else []):
+        for a in [self.tab_dev] + self.elems_dev + (self.stats_dev or []) + ([self.dscore_dev] if self.dscore_dev else []) + ([self.cv_dev] if self.cv_dev else []):
             a.free()
+        if self.cv_host:
+            self.lib.x264hip_host_free(C.c_void_p(self.cv_host))
+            self.cv_host = None
         if self.tab_host:
             self.lib.x264hip_host_free(C.c_void_p(self.tab_host))
             self.tab_host = None
@@ -470,6 +498,9 @@ class AsyncStreamEncoder(StreamEncoder):
         self.pic_events = {}                             # per picture number: what says "in place" to the sweeps that read it (_prepare_picture)
         self.coded_all = [[] for _ in range(B)]          # per chain: the Coded records of its frames, in coding order
         self.next_frame, self.cost_batches, self.undecided = {}, [], set()
+        if self.cavlc:
+            raise ValueError("AsyncStreamEncoder: cabac=0: the CAVLC pass follows a step's whole sweep on one stream (StreamEncoder); here a launch's B kernel "
+                             "ends on a stream of its own")
         if self.post_scenecut:
             raise ValueError("AsyncStreamEncoder: the post-encode scene cut's check is made per step (StreamEncoder); run with pre_scenecut=1")
         if self.direct_auto:
