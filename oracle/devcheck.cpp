@@ -1,5 +1,6 @@
 // devcheck.cpp -- TEST INFRASTRUCTURE.  Host build of the scalar (one-lane) device code of the slice kernel -- the CABAC
-// writer / bit counter of x264_vs2008_amd/csrc/cabac_dev.h and the trellis quantiser of trellis_dev.h -- so that the CPU twin
+// writer / bit counter of x264_vs2008_amd/csrc/cabac_dev.h (over the syntax vocabulary of mb_vocab.h) and the trellis quantiser of
+// trellis_dev.h -- so that the CPU twin
 // (oracle/slice_oracle.c built with -DX264O_DEVCHECK) can replay every call it makes through the product's own text and
 // compare: same context states, same bit counts, same bytes.  No GPU involved; the lane-parallel parts are tested on the GPU.
 #define X264HIP_HOST_TEST 1

@@ -1689,6 +1689,8 @@ static void save_mb(ssl *S, smb *m)
         m->qp = 0; S->last_dqp = 0; m->cbp_chroma = 2; m->cbp_luma = 0xf; m->t8 = 0; cbp_dc = 7;
         memset(m->nnz, 16, 27);                           /* the harness reports 16 for every entry of an I_PCM macroblock */
     } else {                                             /* :1268-1272: a macroblock without coefficients has no QP of its own */
+        /* ... and cavlc_qp_delta's side effect (R/encoder/cavlc.c:205-211), which the next macroblock's QP reads: an I_16x16 without any coefficient */
+        if (!S->p->cabac && m->type == S_I_16x16 && !(m->cbp_luma | m->cbp_chroma | m->nnz[24])) m->qp = S->last_qp;
         if (m->type != S_I_16x16 && m->cbp_luma == 0 && m->cbp_chroma == 0) m->qp = S->last_qp;
         S->last_dqp = m->qp - S->last_qp;
         S->last_qp = m->qp;
@@ -1826,7 +1828,7 @@ static int s_encode_chain(const slice_params *p, const slice_ext *e, const u8 *s
     if (b_write && !p->cabac) return -3;
     if (e && e->psy_trellis != 0) return -3;
     const int nb = e ? clip3i(e->bframes, 0, 16) : 0;
-    if (nb && (!b_write || p->qp == 0 || p->noise_reduction || (e->direct_pred != 1 && e->direct_pred != 2) || p->subme < 1)) return -3;   /* B slices: CABAC with the writer in the loop */
+    if (nb && ((!b_write && p->cabac) || p->qp == 0 || p->noise_reduction || (e->direct_pred != 1 && e->direct_pred != 2) || p->subme < 1)) return -3;   /* B slices: CABAC with the writer in the loop, or the decisions alone of a CAVLC slice */
     memset(&S, 0, sizeof(S));
     S.p = p; S.o = o; S.e = e; S.o2 = o2;
     S.chroma_qp_offset = p->chroma_qp_offset;

@@ -12,16 +12,8 @@
 // The file is plain C++ so that the same text also compiles for the host (-DX264HIP_HOST_TEST): tests/ drive it there
 // against the CPU restatement on every macroblock of a chain (no GPU needed), which is how it was brought up.
 #pragma once
-#include <stdint.h>
-#ifdef X264HIP_HOST_TEST
-#include <string.h>
-#include <stdlib.h>
-#define CD_FN static inline
-#define __device__
-typedef uint8_t u8; typedef int16_t i16; typedef uint16_t u16; typedef uint32_t u32;
-#else
-#define CD_FN __device__ __forceinline__
-#endif
+#include "mb_vocab.h"
+#define CD_FN MB_FN
 #include "cabac_tables.h"
 
 #include "mbsyn.h"
@@ -46,34 +38,16 @@ static __shared__ u8 cd_lds_sig8[64], cd_lds_last8[64];
 #define CD_LAST8(i_) ((int)cd_lds_last8[i_])
 #endif
 
-enum { CD_I_4x4 = 0, CD_I_8x8 = 1, CD_I_16x16 = 2, CD_I_PCM = 3, CD_P_L0 = 4, CD_P_8x8 = 5, CD_P_SKIP = 6,
-       CD_B_DIRECT = 7, CD_B_L0_L0 = 8, CD_B_8x8 = 17, CD_B_SKIP = 18 };
-enum { CD_D_L0_4x4 = 0, CD_D_L0_8x4 = 1, CD_D_L0_4x8 = 2, CD_D_L0_8x8 = 3, CD_D_L1_8x8 = 7, CD_D_BI_8x8 = 11, CD_D_DIRECT_8x8 = 12,
-       CD_D_8x8 = 13, CD_D_16x8 = 14, CD_D_8x16 = 15, CD_D_16x16 = 16 };
-#define CD_IS_SKIP(t_) ((t_) == CD_P_SKIP || (t_) == CD_B_SKIP)
 // the motion caches of either list
 #define CD_CREF(m_, l_) ((l_) ? (m_).cref1 : (m_).cref)
 #define CD_CMV(m_, l_) ((l_) ? (m_).cmv1 : (m_).cmv)
 #define CD_CMVD(m_, l_) ((l_) ? (m_).cmvd1 : (m_).cmvd)
-// x264_mb_type_list_table (R/common/macroblock.h:94-106): does partition `part` of B type `t` (B_L0_L0 .. B_BI_BI) use list `l`?
-// rows: L0L0 L0L1 L0BI L1L0 L1L1 L1BI BIL0 BIL1 BIBI; four bits each: l0p0 l0p1 l1p0 l1p1
-#define CD_B_USES(t_, l_, part_) ((int)((0xfd7ec6b93ull >> (4 * ((t_) - CD_B_L0_L0) + 2 * (l_) + (part_))) & 1))
 // x264_cabac_mb_type's bin strings of the 9 list combinations x {16x8, 8x16, 16x16} (R/encoder/cabac.c:150-176): length << 8 | bins, first bin in bit 0
 static __device__ const u16 d_cw_b_bins[27] = {0x623, 0x613, 0x301, 0x62b, 0x61b, 0x0, 0x707, 0x747, 0x0, 0x63b, 0x61f, 0x0, 0x633, 0x60b, 0x305,
                                                0x727, 0x767, 0x0, 0x717, 0x757, 0x0, 0x737, 0x777, 0x0, 0x70f, 0x74f, 0x603};
-// x264_mb_partition_listX_table for the 8x8 sub-partitions (:140-156)
-#define CD_SUB_USES(s_, l_) ((s_) == CD_D_DIRECT_8x8 ? 0 : (l_) ? ((s_) >= 4 && (s_) <= 11) : ((s_) <= 3 || ((s_) >= 8 && (s_) <= 11)))
-
 CD_FN int cd_clip3(int v, int lo, int hi) { return v < lo ? lo : v > hi ? hi : v; }
 CD_FN int cd_abs(int v) { return v < 0 ? -v : v; }
 CD_FN int cd_ue_size(unsigned v) { int n = 0; v++; while (v >> (n + 1)) n++; return 2 * n + 1; }      // bs_size_ue_big
-CD_FN int cd_scan8(int i)
-{   // x264_scan8, R/common/common.h:196-238
-    if (i < 16) return 4 + 1 * 8 + ((i & 1) | ((i >> 1) & 2)) + 8 * (((i >> 1) & 1) | ((i >> 2) & 2));
-    if (i < 20) return 1 + 1 * 8 + ((i - 16) & 1) + 8 * ((i - 16) >> 1);
-    if (i < 24) return 1 + 4 * 8 + ((i - 20) & 1) + 8 * ((i - 20) >> 1);
-    return 4 + 5 * 8 + (i - 24);
-}
 
 // x264_cabac_context_init, R/common/cabac.c:787-805: state i of the 460 (call with i = lane, lane + 64, ...)
 CD_FN int cd_context_init_one(int i, int slice_type, int qp, int model)
@@ -166,41 +140,20 @@ template <class ST> CD_FN int cd_unary(ST st, int ctx, int prefix)
     return bits + 256;
 }
 
-CD_FN int cd_median(int a, int b, int c) { const int mx = a > b ? a : b, mn = a < b ? a : b; return c > mx ? mx : c < mn ? mn : c; }
-// x264_mb_predict_mv (R/common/macroblock.c:28-88) on the syntax record's motion cache
+// x264_mb_predict_mv on the syntax record's motion cache
 template <class MS> CD_FN void cd_predict_mv(const MS &m, int list, int idx, int width, int &px, int &py)
 {
-    const int i8 = cd_scan8(idx), i_ref = CD_CREF(m, list)[i8];
-    int ra = CD_CREF(m, list)[i8 - 1], rb = CD_CREF(m, list)[i8 - 8], kc = i8 - 8 + width, rc = CD_CREF(m, list)[kc];
-    if ((idx & 3) == 3 || (width == 2 && (idx & 3) == 2) || rc == -2) { kc = i8 - 8 - 1; rc = CD_CREF(m, list)[kc]; }
-    const int ax = CD_CMV(m, list)[i8 - 1][0], ay = CD_CMV(m, list)[i8 - 1][1], bx = CD_CMV(m, list)[i8 - 8][0], by = CD_CMV(m, list)[i8 - 8][1],
-              cx = CD_CMV(m, list)[kc][0], cy = CD_CMV(m, list)[kc][1];
-    if (m.partition == CD_D_16x8) {
-        if (idx == 0 && rb == i_ref) { px = bx; py = by; return; }
-        if (idx != 0 && ra == i_ref) { px = ax; py = ay; return; }
-    } else if (m.partition == CD_D_8x16) {
-        if (idx == 0 && ra == i_ref) { px = ax; py = ay; return; }
-        if (idx != 0 && rc == i_ref) { px = cx; py = cy; return; }
-    }
-    const int cnt = (ra == i_ref) + (rb == i_ref) + (rc == i_ref);
-    if (cnt > 1) { px = cd_median(ax, bx, cx); py = cd_median(ay, by, cy); }
-    else if (cnt == 1) { if (ra == i_ref) { px = ax; py = ay; } else if (rb == i_ref) { px = bx; py = by; } else { px = cx; py = cy; } }
-    else if (rb == -2 && rc == -2 && ra != -2) { px = ax; py = ay; }
-    else { px = cd_median(ax, bx, cx); py = cd_median(ay, by, cy); }
+    mb_predict_mv([&](int k) -> int { return CD_CREF(m, list)[k]; }, [&](int k) -> int { return CD_CMV(m, list)[k][0]; },
+                  [&](int k) -> int { return CD_CMV(m, list)[k][1]; }, m.partition, idx, width, px, py);
 }
-CD_FN int cd_fix4(int m) { return m < 0 ? -1 : m < 9 ? m : 2; }          // x264_mb_pred_mode4x4_fix
-template <class MS> CD_FN int cd_pred_i4mode(const MS &m, int idx)
-{   // x264_mb_predict_intra4x4_mode, R/common/macroblock.h:423-434
-    const int ma = cd_fix4(m.i4c[cd_scan8(idx) - 1]), mb = cd_fix4(m.i4c[cd_scan8(idx) - 8]), v = ma < mb ? ma : mb;
-    return v < 0 ? 2 : v;
-}
+template <class MS> CD_FN int cd_pred_i4mode(const MS &m, int idx) { return mb_pred_i4mode(m.i4c[mb_scan8(idx) - 1], m.i4c[mb_scan8(idx) - 8]); }
 
 template <class ST, class MS> CD_FN void cw_mb_type_intra(DCabac &cb, ST st, int rd, const MS &m, int c0, int c1, int c2, int c3, int c4, int c5, int i_frame)
 {   // x264_cabac_mb_type_intra, R/encoder/cabac.c:32-62
-    if (m.type == CD_I_4x4 || m.type == CD_I_8x8) cdd_noup(cb, st, rd, c0, 0);
-    else if (m.type == CD_I_PCM) { cdd_noup(cb, st, rd, c0, 1); if (!rd) cd_encode_flush(cb, i_frame); }
+    if (m.type == T_I_4x4 || m.type == T_I_8x8) cdd_noup(cb, st, rd, c0, 0);
+    else if (m.type == T_I_PCM) { cdd_noup(cb, st, rd, c0, 1); if (!rd) cd_encode_flush(cb, i_frame); }
     else {
-        const int pred = m.i16mode < 4 ? m.i16mode : 2;          // x264_mb_pred_mode16x16_fix
+        const int pred = mb_fix16(m.i16mode);
         cdd_noup(cb, st, rd, c0, 1);
         if (!rd) cd_encode_terminal(cb); else cb.f8 += CD_ENT(st[276], 0);
         cdd_noup(cb, st, rd, c1, !!m.cbp_luma);
@@ -213,22 +166,22 @@ template <class ST, class MS> CD_FN void cw_mb_type_intra(DCabac &cb, ST st, int
 template <class ST, class MS> CD_FN void cw_mb_type(DCabac &cb, ST st, int rd, const MS &m, int i_frame)
 {   // x264_cabac_mb_type, :64-196
     if (m.slice_type == 2) {
-        const int ctx = (m.type_left >= 0 && m.type_left != CD_I_4x4) + (m.type_top >= 0 && m.type_top != CD_I_4x4);
+        const int ctx = (m.type_left >= 0 && m.type_left != T_I_4x4) + (m.type_top >= 0 && m.type_top != T_I_4x4);
         cw_mb_type_intra(cb, st, rd, m, 3 + ctx, 3 + 3, 3 + 4, 3 + 5, 3 + 6, 3 + 7, i_frame);
     } else if (m.slice_type == 1) {                       // :126-190
-        const int ctx = (m.type_left >= 0 && m.type_left != CD_B_SKIP && m.type_left != CD_B_DIRECT)
-                      + (m.type_top >= 0 && m.type_top != CD_B_SKIP && m.type_top != CD_B_DIRECT);
-        if (m.type == CD_B_DIRECT) cdd_noup(cb, st, rd, 27 + ctx, 0);
-        else if (m.type == CD_B_8x8) {
+        const int ctx = (m.type_left >= 0 && m.type_left != T_B_SKIP && m.type_left != T_B_DIRECT)
+                      + (m.type_top >= 0 && m.type_top != T_B_SKIP && m.type_top != T_B_DIRECT);
+        if (m.type == T_B_DIRECT) cdd_noup(cb, st, rd, 27 + ctx, 0);
+        else if (m.type == T_B_8x8) {
             cdd_noup(cb, st, rd, 27 + ctx, 1); cdd_noup(cb, st, rd, 27 + 3, 1); cdd_noup(cb, st, rd, 27 + 4, 1);
             cdd(cb, st, rd, 27 + 5, 1); cdd(cb, st, rd, 27 + 5, 1); cdd_noup(cb, st, rd, 27 + 5, 1);
-        } else if (m.type <= CD_I_PCM) {
+        } else if (m.type <= T_I_PCM) {
             cdd_noup(cb, st, rd, 27 + ctx, 1); cdd_noup(cb, st, rd, 27 + 3, 1); cdd_noup(cb, st, rd, 27 + 4, 1);
             cdd(cb, st, rd, 27 + 5, 1); cdd(cb, st, rd, 27 + 5, 0); cdd(cb, st, rd, 27 + 5, 1);
             cw_mb_type_intra(cb, st, rd, m, 32 + 0, 32 + 1, 32 + 2, 32 + 2, 32 + 3, 32 + 3, i_frame);
         } else {
             // the bin strings of the 16x8 / 8x16 / 16x16 forms of the nine list combinations: length << 8 | bits, first bin in bit 0
-            const int idx = (m.type - CD_B_L0_L0) * 3 + (m.partition - CD_D_16x8);
+            const int idx = (m.type - T_B_L0_L0) * 3 + (m.partition - D_16x8);
             const u32 code = d_cw_b_bins[idx];
             const int len = (int)(code >> 8), b1 = (int)((code >> 1) & 1);
             cdd_noup(cb, st, rd, 27 + ctx, (int)(code & 1));
@@ -236,11 +189,11 @@ template <class ST, class MS> CD_FN void cw_mb_type(DCabac &cb, ST st, int rd, c
             cdd(cb, st, rd, 27 + 5 - b1, (int)((code >> 2) & 1));
             for (int i = 3; i < len; i++) cdd(cb, st, rd, 27 + 5, (int)((code >> i) & 1));
         }
-    } else if (m.type == CD_P_L0) {
+    } else if (m.type == T_P_L0) {
         cdd_noup(cb, st, rd, 14, 0);
-        if (m.partition == CD_D_16x16) { cdd_noup(cb, st, rd, 15, 0); cdd_noup(cb, st, rd, 16, 0); }
-        else { cdd_noup(cb, st, rd, 15, 1); cdd_noup(cb, st, rd, 17, m.partition == CD_D_16x8); }
-    } else if (m.type == CD_P_8x8) {
+        if (m.partition == D_16x16) { cdd_noup(cb, st, rd, 15, 0); cdd_noup(cb, st, rd, 16, 0); }
+        else { cdd_noup(cb, st, rd, 15, 1); cdd_noup(cb, st, rd, 17, m.partition == D_16x8); }
+    } else if (m.type == T_P_8x8) {
         cdd_noup(cb, st, rd, 14, 0); cdd_noup(cb, st, rd, 15, 0); cdd_noup(cb, st, rd, 16, 1);
     } else {
         cdd_noup(cb, st, rd, 14, 1);
@@ -256,7 +209,7 @@ template <class ST> CD_FN void cw_intra4x4_pred_mode(DCabac &cb, ST st, int rd, 
 }
 template <class ST, class MS> CD_FN void cw_chroma_pred_mode(DCabac &cb, ST st, int rd, const MS &m)
 {   // :213-231
-    const int mode = m.chroma_mode < 4 ? m.chroma_mode : 0, ctx = (m.cpm_left != 0) + (m.cpm_top != 0);     // x264_mb_pred_mode8x8c_fix
+    const int mode = mb_fix8c(m.chroma_mode), ctx = (m.cpm_left != 0) + (m.cpm_top != 0);
     cdd_noup(cb, st, rd, 64 + ctx, mode > 0);
     if (mode > 0) {
         cdd(cb, st, rd, 64 + 3, mode > 1);
@@ -292,7 +245,7 @@ template <class ST, class MS> CD_FN void cw_cbp_chroma(DCabac &cb, ST st, int rd
 template <class ST, class MS> CD_FN void cw_qp_delta(DCabac &cb, ST st, int rd, MS &m)
 {   // :265-297
     int dqp = m.qp - m.last_qp, ctx;
-    if (m.type == CD_I_16x16 && !(m.cbp_luma | m.cbp_chroma | m.nnz[24] | m.nnz[25] | m.nnz[26])) {
+    if (m.type == T_I_16x16 && !(m.cbp_luma | m.cbp_chroma | m.nnz[24] | m.nnz[25] | m.nnz[26])) {
         if (!rd) m.qp = m.last_qp;
         dqp = 0;
     }
@@ -307,27 +260,27 @@ template <class ST, class MS> CD_FN void cw_qp_delta(DCabac &cb, ST st, int rd, 
 // x264_cabac_mb_skip, :300-306
 template <class ST> CD_FN void cw_mb_skip(DCabac &cb, ST st, int type_left, int type_top, int b_skip, int slice_type = 0)
 {
-    const int ctx = (type_left >= 0 && !CD_IS_SKIP(type_left)) + (type_top >= 0 && !CD_IS_SKIP(type_top)) + (slice_type == 0 ? 11 : 24);
+    const int ctx = (type_left >= 0 && !IS_SKIP_T(type_left)) + (type_top >= 0 && !IS_SKIP_T(type_top)) + (slice_type == 0 ? 11 : 24);
     cd_encode_decision(cb, st, ctx, b_skip);
 }
 template <class ST> CD_FN void cw_sub_b_partition(DCabac &cb, ST st, int rd, int sub)
 {   // x264_cabac_mb_sub_b_partition, :332-367 (only the 8x8 shapes: x264 uses no smaller B partition)
-    if (sub == CD_D_DIRECT_8x8) { cdd(cb, st, rd, 36, 0); return; }
+    if (sub == D_DIRECT_8x8) { cdd(cb, st, rd, 36, 0); return; }
     cdd(cb, st, rd, 36, 1);
-    if (sub == CD_D_BI_8x8) { cdd(cb, st, rd, 37, 1); cdd(cb, st, rd, 38, 0); cdd(cb, st, rd, 39, 0); cdd(cb, st, rd, 39, 0); }
-    else { cdd(cb, st, rd, 37, 0); cdd(cb, st, rd, 39, sub == CD_D_L1_8x8); }
+    if (sub == D_BI_8x8) { cdd(cb, st, rd, 37, 1); cdd(cb, st, rd, 38, 0); cdd(cb, st, rd, 39, 0); cdd(cb, st, rd, 39, 0); }
+    else { cdd(cb, st, rd, 37, 0); cdd(cb, st, rd, 39, sub == D_L1_8x8); }
 }
 template <class ST> CD_FN void cw_sub_p_partition(DCabac &cb, ST st, int rd, int sub)
 {   // :309-330
-    if (sub == CD_D_L0_8x8) { cdd(cb, st, rd, 21, 1); return; }
+    if (sub == D_L0_8x8) { cdd(cb, st, rd, 21, 1); return; }
     cdd(cb, st, rd, 21, 0);
-    if (sub == CD_D_L0_8x4) { cdd(cb, st, rd, 22, 0); return; }
+    if (sub == D_L0_8x4) { cdd(cb, st, rd, 22, 0); return; }
     cdd(cb, st, rd, 22, 1);
-    cdd(cb, st, rd, 23, sub == CD_D_L0_4x8);
+    cdd(cb, st, rd, 23, sub == D_L0_4x8);
 }
 template <class ST, class MS> CD_FN void cw_ref(DCabac &cb, ST st, int rd, const MS &m, int idx, int list = 0)
 {   // x264_cabac_mb_ref, :375-395 (h->mb.cache.skip is all zero in a P slice)
-    const int i8 = cd_scan8(idx), refa = CD_CREF(m, list)[i8 - 1], refb = CD_CREF(m, list)[i8 - 8];
+    const int i8 = mb_scan8(idx), refa = CD_CREF(m, list)[i8 - 1], refb = CD_CREF(m, list)[i8 - 8];
     int ref = CD_CREF(m, list)[i8], ctx = (refa > 0) + 2 * (refb > 0);
     if (m.slice_type == 1) ctx = (refa > 0 && !m.cskip[i8 - 1]) + 2 * (refb > 0 && !m.cskip[i8 - 8]);
     for (; ref > 0; ref--) { cdd(cb, st, rd, 54 + ctx, 1); ctx = (ctx >> 2) + 4; }
@@ -335,7 +288,7 @@ template <class ST, class MS> CD_FN void cw_ref(DCabac &cb, ST st, int rd, const
 }
 template <class ST, class MS> CD_FN void cw_mvd_cpn(DCabac &cb, ST st, int rd, const MS &m, int list, int idx, int l, int mvd)
 {   // x264_cabac_mb_mvd_cpn, :397-445
-    const int i8 = cd_scan8(idx), amvd = cd_abs(CD_CMVD(m, list)[i8 - 1][l]) + cd_abs(CD_CMVD(m, list)[i8 - 8][l]), a = cd_abs(mvd), base = l ? 47 : 40;
+    const int i8 = mb_scan8(idx), amvd = cd_abs(CD_CMVD(m, list)[i8 - 1][l]) + cd_abs(CD_CMVD(m, list)[i8 - 8][l]), a = cd_abs(mvd), base = l ? 47 : 40;
     const int ctx = (amvd > 2) + (amvd > 32);
 #define CD_MVCTX(i_) ((i_) < 4 ? (i_) + 2 : 6)                             /* ctxes[] = {0,3,4,5,6,6,6,6,6} for i >= 1 */
     if (a == 0) { cdd(cb, st, rd, base + ctx, 0); return; }
@@ -364,7 +317,7 @@ template <class ST, class MS> CD_FN void cw_mvd_cpn(DCabac &cb, ST st, int rd, c
 template <class ST, class MS> CD_FN void cw_mvd(DCabac &cb, ST st, int rd, MS &m, int idx, int width, int height, int list = 0)
 {   // x264_cabac_mb_mvd, :447-463
     int px, py;
-    const int i8 = cd_scan8(idx);
+    const int i8 = mb_scan8(idx);
     cd_predict_mv(m, list, idx, width, px, py);
     const int dx = CD_CMV(m, list)[i8][0] - px, dy = CD_CMV(m, list)[i8][1] - py;
     cw_mvd_cpn(cb, st, rd, m, list, idx, 0, dx);
@@ -375,9 +328,9 @@ template <class ST, class MS> CD_FN void cw_mvd(DCabac &cb, ST st, int rd, MS &m
 template <class ST, class MS> CD_FN void cw_mb8x8_mvd(DCabac &cb, ST st, int rd, MS &m, int i)
 {   // :465-498 (list 0)
     const int sub = m.sub[i];
-    if (sub == CD_D_L0_8x8) cw_mvd(cb, st, rd, m, 4 * i, 2, 2);
-    else if (sub == CD_D_L0_8x4) { cw_mvd(cb, st, rd, m, 4 * i, 2, 1); cw_mvd(cb, st, rd, m, 4 * i + 2, 2, 1); }
-    else if (sub == CD_D_L0_4x8) { cw_mvd(cb, st, rd, m, 4 * i, 1, 2); cw_mvd(cb, st, rd, m, 4 * i + 1, 1, 2); }
+    if (sub == D_L0_8x8) cw_mvd(cb, st, rd, m, 4 * i, 2, 2);
+    else if (sub == D_L0_8x4) { cw_mvd(cb, st, rd, m, 4 * i, 2, 1); cw_mvd(cb, st, rd, m, 4 * i + 2, 2, 1); }
+    else if (sub == D_L0_4x8) { cw_mvd(cb, st, rd, m, 4 * i, 1, 2); cw_mvd(cb, st, rd, m, 4 * i + 1, 1, 2); }
     else for (int k = 0; k < 4; k++) cw_mvd(cb, st, rd, m, 4 * i + k, 1, 1);
 }
 
@@ -395,7 +348,7 @@ template <class MS> CD_FN int cd_nz_top(const MS &m, int idx)
 }
 template <class MS> CD_FN int cw_cbf_ctx(const MS &m, int cat, int idx)
 {   // x264_cabac_mb_cbf_ctxidxinc, :508-538
-    const int intra = m.type <= CD_I_PCM;
+    const int intra = m.type <= T_I_PCM;
     int a, b;
     if (cat == 1 || cat == 2 || cat == 4) {
         a = cd_nz_left(m, idx) & (0x7f + (intra << 7)); b = cd_nz_top(m, idx) & (0x7f + (intra << 7));
@@ -505,55 +458,55 @@ template <class ST, class MS, class FE> CD_FN void cw_macroblock(DCabac &cb, ST 
 {
     const int type = m.type;
     cw_mb_type(cb, st, rd, m, i_frame);
-    if (!rd && type == CD_I_PCM) {
+    if (!rd && type == T_I_PCM) {
         for (int i = 0; i < 384; i++) *cb.p++ = fe[i];
         cb.low = 0; cb.range = 0x1FE; cb.queue = -1; cb.outstanding = 0;
         return;
     }
-    if (type <= CD_I_PCM) {
-        if (m.pps_t8 && type != CD_I_16x16) cdd_noup(cb, st, rd, 399 + m.nb_t8, m.t8);
-        if (type != CD_I_16x16)
-            for (int i = 0; i < 16; i += type == CD_I_8x8 ? 4 : 1)
-                cw_intra4x4_pred_mode(cb, st, rd, cd_pred_i4mode(m, i), cd_fix4(m.i4c[cd_scan8(i)]));
+    if (type <= T_I_PCM) {
+        if (m.pps_t8 && type != T_I_16x16) cdd_noup(cb, st, rd, 399 + m.nb_t8, m.t8);
+        if (type != T_I_16x16)
+            for (int i = 0; i < 16; i += type == T_I_8x8 ? 4 : 1)
+                cw_intra4x4_pred_mode(cb, st, rd, cd_pred_i4mode(m, i), mb_fix4(m.i4c[mb_scan8(i)]));
         cw_chroma_pred_mode(cb, st, rd, m);
-    } else if (type == CD_P_L0) {
+    } else if (type == T_P_L0) {
         const int multi = m.n_ref > 1;
-        if (m.partition == CD_D_16x16) {
+        if (m.partition == D_16x16) {
             if (multi) cw_ref(cb, st, rd, m, 0);
             cw_mvd(cb, st, rd, m, 0, 4, 4);
-        } else if (m.partition == CD_D_16x8) {
+        } else if (m.partition == D_16x8) {
             if (multi) { cw_ref(cb, st, rd, m, 0); cw_ref(cb, st, rd, m, 8); }
             cw_mvd(cb, st, rd, m, 0, 4, 2); cw_mvd(cb, st, rd, m, 8, 4, 2);
         } else {
             if (multi) { cw_ref(cb, st, rd, m, 0); cw_ref(cb, st, rd, m, 4); }
             cw_mvd(cb, st, rd, m, 0, 2, 4); cw_mvd(cb, st, rd, m, 4, 2, 4);
         }
-    } else if (type == CD_P_8x8) {
+    } else if (type == T_P_8x8) {
         for (int i = 0; i < 4; i++) cw_sub_p_partition(cb, st, rd, m.sub[i]);
         if (m.n_ref > 1) for (int i = 0; i < 4; i++) cw_ref(cb, st, rd, m, 4 * i);
         for (int i = 0; i < 4; i++) cw_mb8x8_mvd(cb, st, rd, m, i);
-    } else if (type == CD_B_8x8) {                           // :894-916
+    } else if (type == T_B_8x8) {                           // :894-916
         for (int i = 0; i < 4; i++) cw_sub_b_partition(cb, st, rd, m.sub[i]);
         for (int l = 0; l < 2; l++) {
             if ((l ? m.n_ref1 : m.n_ref) == 1) continue;
-            for (int i = 0; i < 4; i++) if (CD_SUB_USES(m.sub[i], l)) cw_ref(cb, st, rd, m, 4 * i, l);
+            for (int i = 0; i < 4; i++) if (SUB_USES(m.sub[i], l)) cw_ref(cb, st, rd, m, 4 * i, l);
         }
         for (int l = 0; l < 2; l++)
-            for (int i = 0; i < 4; i++) if (CD_SUB_USES(m.sub[i], l)) cw_mvd(cb, st, rd, m, 4 * i, 2, 2, l);
-    } else if (type > CD_B_DIRECT && type < CD_B_8x8) {      // :917-962: the B types with explicit lists
-        const int n = m.partition == CD_D_16x16 ? 1 : 2, step = m.partition == CD_D_16x8 ? 8 : 4;
-        const int w = m.partition == CD_D_8x16 ? 2 : 4, h = m.partition == CD_D_16x8 ? 2 : 4;
+            for (int i = 0; i < 4; i++) if (SUB_USES(m.sub[i], l)) cw_mvd(cb, st, rd, m, 4 * i, 2, 2, l);
+    } else if (type > T_B_DIRECT && type < T_B_8x8) {      // :917-962: the B types with explicit lists
+        const int n = m.partition == D_16x16 ? 1 : 2, step = m.partition == D_16x8 ? 8 : 4;
+        const int w = m.partition == D_8x16 ? 2 : 4, h = m.partition == D_16x8 ? 2 : 4;
         for (int l = 0; l < 2; l++)
             if ((l ? m.n_ref1 : m.n_ref) > 1)
-                for (int i = 0; i < n; i++) if (CD_B_USES(type, l, i)) cw_ref(cb, st, rd, m, step * i, l);
+                for (int i = 0; i < n; i++) if (B_USES(type, l, i)) cw_ref(cb, st, rd, m, step * i, l);
         for (int l = 0; l < 2; l++)
-            for (int i = 0; i < n; i++) if (CD_B_USES(type, l, i)) cw_mvd(cb, st, rd, m, step * i, w, h, l);
+            for (int i = 0; i < n; i++) if (B_USES(type, l, i)) cw_mvd(cb, st, rd, m, step * i, w, h, l);
     }
-    if (type != CD_I_16x16) cw_cbp(cb, st, rd, m);
+    if (type != T_I_16x16) cw_cbp(cb, st, rd, m);
     if (m.t8_allowed && m.cbp_luma) cdd_noup(cb, st, rd, 399 + m.nb_t8, m.t8);
-    if (m.cbp_luma > 0 || m.cbp_chroma > 0 || type == CD_I_16x16) {
+    if (m.cbp_luma > 0 || m.cbp_chroma > 0 || type == T_I_16x16) {
         cw_qp_delta(cb, st, rd, m);
-        if (type == CD_I_16x16) {
+        if (type == T_I_16x16) {
             cw_residual(cb, st, rd, m, 0, 24, &m.lv_dc[0], 16);
             if (m.cbp_luma) for (int i = 0; i < 16; i++) cw_residual(cb, st, rd, m, 1, i, &m.lv4[i][1], 15);
         } else if (m.t8) {
@@ -569,14 +522,14 @@ template <class ST, class MS, class FE> CD_FN void cw_macroblock(DCabac &cb, ST 
 // "doesn't write cbp or chroma dc, doesn't write ref or subpartition".  pix: 1 16x8, 2 8x16, 3 8x8 (4 8x4, 5 4x8, 6 4x4 for sub-partitions)
 template <class ST, class MS> CD_FN void cw_partition_size(DCabac &cb, ST st, MS &m, int i8, int pix)
 {   // x264_partition_size_cabac, :1032-1081
-    const int b_8x16 = m.partition == CD_D_8x16;
-    if (m.type == CD_P_8x8) cw_mb8x8_mvd(cb, st, 1, m, i8);
-    else if (m.type == CD_P_L0) cw_mvd(cb, st, 1, m, 4 * i8, 4 >> b_8x16, 2 << b_8x16);
-    else if (m.type > CD_B_DIRECT && m.type < CD_B_8x8) {
-        if (CD_B_USES(m.type, 0, !!i8)) cw_mvd(cb, st, 1, m, 4 * i8, 4 >> b_8x16, 2 << b_8x16, 0);
-        if (CD_B_USES(m.type, 1, !!i8)) cw_mvd(cb, st, 1, m, 4 * i8, 4 >> b_8x16, 2 << b_8x16, 1);
-    } else if (m.type == CD_B_8x8) {
-        for (int l = 0; l < 2; l++) if (CD_SUB_USES(m.sub[i8], l)) cw_mvd(cb, st, 1, m, 4 * i8, 2, 2, l);
+    const int b_8x16 = m.partition == D_8x16;
+    if (m.type == T_P_8x8) cw_mb8x8_mvd(cb, st, 1, m, i8);
+    else if (m.type == T_P_L0) cw_mvd(cb, st, 1, m, 4 * i8, 4 >> b_8x16, 2 << b_8x16);
+    else if (m.type > T_B_DIRECT && m.type < T_B_8x8) {
+        if (B_USES(m.type, 0, !!i8)) cw_mvd(cb, st, 1, m, 4 * i8, 4 >> b_8x16, 2 << b_8x16, 0);
+        if (B_USES(m.type, 1, !!i8)) cw_mvd(cb, st, 1, m, 4 * i8, 4 >> b_8x16, 2 << b_8x16, 1);
+    } else if (m.type == T_B_8x8) {
+        for (int l = 0; l < 2; l++) if (SUB_USES(m.sub[i8], l)) cw_mvd(cb, st, 1, m, 4 * i8, 2, 2, l);
     } else
         return;
     for (int j = pix < 3; j >= 0; j--) {
@@ -601,13 +554,13 @@ template <class ST, class MS> CD_FN void cw_subpartition_size(DCabac &cb, ST st,
 }
 template <class ST, class MS> CD_FN void cw_partition_i8x8_size(DCabac &cb, ST st, const MS &m, int i8, int mode)
 {   // x264_partition_i8x8_size_cabac, :1097-1105
-    cw_intra4x4_pred_mode(cb, st, 1, cd_pred_i4mode(m, 4 * i8), cd_fix4(mode));
+    cw_intra4x4_pred_mode(cb, st, 1, cd_pred_i4mode(m, 4 * i8), mb_fix4(mode));
     cw_cbp_luma(cb, st, 1, m);
     if (m.cbp_luma & (1 << i8)) cw_residual(cb, st, 1, m, 5, 4 * i8, &m.lv8[i8][0], 64);
 }
 template <class ST, class MS> CD_FN void cw_partition_i4x4_size(DCabac &cb, ST st, const MS &m, int i4, int mode)
 {   // x264_partition_i4x4_size_cabac, :1107-1113
-    cw_intra4x4_pred_mode(cb, st, 1, cd_pred_i4mode(m, i4), cd_fix4(mode));
+    cw_intra4x4_pred_mode(cb, st, 1, cd_pred_i4mode(m, i4), mb_fix4(mode));
     cw_residual(cb, st, 1, m, 2, i4, &m.lv4[i4][0], 16);
 }
 template <class ST, class MS> CD_FN void cw_i8x8_chroma_size(DCabac &cb, ST st, const MS &m)

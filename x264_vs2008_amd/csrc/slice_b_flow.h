@@ -69,35 +69,12 @@
     }
     WAVE_SYNC();
 
-    // x264_mb_predict_mv_16x16 from the cache (R/common/macroblock.c:90-128)
+    // x264_mb_predict_mv_16x16 / x264_mb_predict_mv from list l's cache; cur_part = h->mb.i_partition
     auto predict16_b = [&](int l, int i_ref, int &px, int &py) {
-        int ra = CREF(l, 11), rb = CREF(l, 4), rc = CREF(l, 8), kc = 8;
-        if (rc == -2) { kc = 3; rc = CREF(l, 3); }
-        const int ax = CMVX(l, 11), ay = CMVY(l, 11), bx = CMVX(l, 4), byv = CMVY(l, 4), cx = CMVX(l, kc), cy = CMVY(l, kc);
-        const int cnt = (ra == i_ref) + (rb == i_ref) + (rc == i_ref);
-        if (cnt > 1) { px = sw_median(ax, bx, cx); py = sw_median(ay, byv, cy); }
-        else if (cnt == 1) { if (ra == i_ref) { px = ax; py = ay; } else if (rb == i_ref) { px = bx; py = byv; } else { px = cx; py = cy; } }
-        else if (rb == -2 && rc == -2 && ra != -2) { px = ax; py = ay; }
-        else { px = sw_median(ax, bx, cx); py = sw_median(ay, byv, cy); }
+        mb_predict_mv_16x16([&](int k) { return CREF(l, k); }, [&](int k) { return CMVX(l, k); }, [&](int k) { return CMVY(l, k); }, i_ref, px, py);
     };
-    // x264_mb_predict_mv (:28-88) from the cache; cur_part = h->mb.i_partition
     auto predict_blk_b = [&](int l, int cur_part, int idx, int width, int &px, int &py) {
-        const int i8 = sw_scan8(idx), i_ref = CREF(l, i8);
-        int ra = CREF(l, i8 - 1), rb = CREF(l, i8 - 8), kc = i8 - 8 + width, rc = CREF(l, kc);
-        if ((idx & 3) == 3 || (width == 2 && (idx & 3) == 2) || rc == -2) { kc = i8 - 8 - 1; rc = CREF(l, kc); }
-        const int ax = CMVX(l, i8 - 1), ay = CMVY(l, i8 - 1), bx = CMVX(l, i8 - 8), byv = CMVY(l, i8 - 8), cx = CMVX(l, kc), cy = CMVY(l, kc);
-        if (cur_part == 14) {
-            if (idx == 0 && rb == i_ref) { px = bx; py = byv; return; }
-            if (idx != 0 && ra == i_ref) { px = ax; py = ay; return; }
-        } else if (cur_part == 15) {
-            if (idx == 0 && ra == i_ref) { px = ax; py = ay; return; }
-            if (idx != 0 && rc == i_ref) { px = cx; py = cy; return; }
-        }
-        const int cnt = (ra == i_ref) + (rb == i_ref) + (rc == i_ref);
-        if (cnt > 1) { px = sw_median(ax, bx, cx); py = sw_median(ay, byv, cy); }
-        else if (cnt == 1) { if (ra == i_ref) { px = ax; py = ay; } else if (rb == i_ref) { px = bx; py = byv; } else { px = cx; py = cy; } }
-        else if (rb == -2 && rc == -2 && ra != -2) { px = ax; py = ay; }
-        else { px = sw_median(ax, bx, cx); py = sw_median(ay, byv, cy); }
+        mb_predict_mv([&](int k) { return CREF(l, k); }, [&](int k) { return CMVX(l, k); }, [&](int k) { return CMVY(l, k); }, cur_part, idx, width, px, py);
     };
     // quarter-sample luma prediction of four pixels of row r at x (macroblock coordinates) from list l's picture ri (mc_luma / get_ref)
     auto luma4 = [&](int l, int ri, int vx, int vy, int r, int x, int out[4]) {
@@ -192,10 +169,10 @@
     int l_ref0 = 0, l_ref1 = 0;                           // a->l0.i_ref / a->l1.i_ref
 #define LREF(l_) ((l_) ? l_ref1 : l_ref0)
     int cost16bi = MX_COST_MAX, cost16direct = MX_COST_MAX, cost8bi = MX_COST_MAX, cost16x8bi = MX_COST_MAX, cost8x16bi = MX_COST_MAX;
-    int part16x8_0 = 3, part16x8_1 = 3, part8x16_0 = 3, part8x16_1 = 3, type16x8 = T_B_L0_L0, type8x16 = T_B_L0_L0;
+    int part16x8_0 = D_L0_8x8, part16x8_1 = D_L0_8x8, part8x16_0 = D_L0_8x8, part8x16_1 = D_L0_8x8, type16x8 = T_B_L0_L0, type8x16 = T_B_L0_L0;
     int rd_direct = MX_COST_MAX, rd_l0 = MX_COST_MAX, rd_l1 = MX_COST_MAX, rd_bi = MX_COST_MAX, rd_8 = MX_COST_MAX, rd_168 = MX_COST_MAX, rd_816 = MX_COST_MAX;
     auto SUB = [&](int i) -> int { return UNI(sb.sub[i]); };
-    auto sub_uses = [&](int sub, int l) -> bool { return sub == 12 ? false : l ? (sub >= 4 && sub <= 11) : (sub <= 3 || (sub >= 8 && sub <= 11)); };
+    auto sub_uses = [&](int sub, int l) -> bool { return SUB_USES(sub, l); };
 
     // ---- x264_mb_load_mv_direct8x8 / CACHE_MV_BI / x264_analyse_update_cache (B types), then the final vectors the motion compensation reads ----
     auto load_direct8x8 = [&](int idx) {
@@ -232,8 +209,8 @@
     auto update_cache_b = [&]() {
         if (type == T_B_SKIP || type == T_B_DIRECT) { for (int i = 0; i < 4; i++) load_direct8x8(i); }
         else if (type == T_B_8x8) { for (int i = 0; i < 4; i++) cache_mv_b8x8(i, 1); }
-        else if (part == 16) cache_mv_bi(0, 0, 4, 4, 0, type == T_B_L0_L0 ? 3 : type == T_B_L1_L1 ? 7 : 11, 1);
-        else if (part == 14) { cache_mv_bi(0, 0, 4, 2, 5, part16x8_0, 1); cache_mv_bi(0, 2, 4, 2, 6, part16x8_1, 1); }
+        else if (part == D_16x16) cache_mv_bi(0, 0, 4, 4, 0, type == T_B_L0_L0 ? D_L0_8x8 : type == T_B_L1_L1 ? D_L1_8x8 : D_BI_8x8, 1);
+        else if (part == D_16x8) { cache_mv_bi(0, 0, 4, 2, 5, part16x8_0, 1); cache_mv_bi(0, 2, 4, 2, 6, part16x8_1, 1); }
         else { cache_mv_bi(0, 0, 2, 4, 7, part8x16_0, 1); cache_mv_bi(2, 0, 2, 4, 8, part8x16_1, 1); }
         finals_from_cache();
     };
@@ -279,7 +256,7 @@
     enum { BS_PRE, BS_CAND, BS_AFTER_EARLY, BS_AN2, BS_SELECT, BS_T8, BS_I16, BS_I4, BS_I8, BS_FINAL };
     int bstep = BS_PRE, kcand = 0, pass = 0, bthresh = 0, bskip_cost = MX_COST_MAX;
     bool direct_ok = true;          // x264_mb_predict_mv_direct16x16's return value: temporal prediction fails when a co-located reference is not in list 0
-    int i_type_b = T_B_L0_L0, i_part_b = 16, i_cost_b = MX_COST_MAX, i_satd_inter_b = 0;
+    int i_type_b = T_B_L0_L0, i_part_b = D_16x16, i_cost_b = MX_COST_MAX, i_satd_inter_b = 0;
 #pragma nounroll
     for (;;) {
         bool fin = false;
@@ -454,7 +431,7 @@
                 cost16bi = satd_region(tmp, 16, 0, 0, 16, 16) + REFC(0, l_ref0) + ME(0, 0, 3) + ME(1, 0, 3) + Q.lambda * 5;
                 if (lane == 0) { sb.me[0][0][2] += Q.lambda * 3; sb.me[1][0][2] += Q.lambda * 3; }
                 WAVE_SYNC();
-                i_type_b = T_B_L0_L0; i_part_b = 16; i_cost_b = ME(0, 0, 2);
+                i_type_b = T_B_L0_L0; i_part_b = D_16x16; i_cost_b = ME(0, 0, 2);
                 if (ME(1, 0, 2) < i_cost_b) { i_cost_b = ME(1, 0, 2); i_type_b = T_B_L1_L1; }
                 if (cost16bi < i_cost_b) { i_cost_b = cost16bi; i_type_b = T_B_BI_BI; }
                 if (cost16direct < i_cost_b) { i_cost_b = cost16direct; i_type_b = T_B_DIRECT; }
@@ -473,10 +450,10 @@
             if (kcand == 7) { bstep = pass == 0 ? BS_AFTER_EARLY : BS_SELECT; continue; }
             skip_mc = kcand == 0;                                   // "Assumes direct/skip MC is still in fdec"
             if (kcand == 0) type = T_B_DIRECT;
-            else if (kcand < 4) { type = kcand == 1 ? T_B_L0_L0 : kcand == 2 ? T_B_L1_L1 : T_B_BI_BI; part = 16; }
-            else if (kcand == 4) { type = T_B_8x8; part = 13; }
-            else if (kcand == 5) { type = type16x8; part = 14; }
-            else { type = type8x16; part = 15; }
+            else if (kcand < 4) { type = kcand == 1 ? T_B_L0_L0 : kcand == 2 ? T_B_L1_L1 : T_B_BI_BI; part = D_16x16; }
+            else if (kcand == 4) { type = T_B_8x8; part = D_8x8; }
+            else if (kcand == 5) { type = type16x8; part = D_16x8; }
+            else { type = type8x16; part = D_8x16; }
         } else if (bstep == BS_AFTER_EARLY) {
             if (bskip_cost < rd_direct && bskip_cost < rd_bi && bskip_cost < rd_l0 && bskip_cost < rd_l1) { type = T_B_SKIP; skip_mc = 0; fin = true; }
             else { bstep = BS_AN2; continue; }
@@ -518,7 +495,7 @@
                 }
                 cost8bi += Q.lambda * 9;
                 if (cost8bi < i_cost_b) {
-                    i_type_b = T_B_8x8; i_part_b = 13; i_cost_b = cost8bi;
+                    i_type_b = T_B_8x8; i_part_b = D_8x8; i_cost_b = cost8bi;
 #pragma nounroll
                     for (int dir = 0; dir < 2; dir++) {          // 0: x264_mb_analyse_inter_b16x8, 1: _b8x16
                         if (dir == 0 ? !(SUB(0) == SUB(1) || SUB(2) == SUB(3)) : !(SUB(0) == SUB(2) || SUB(1) == SUB(3))) continue;
@@ -529,7 +506,7 @@
                             for (int l = 0; l < 2; l++) {
                                 int px, py, vx, vy, cm;
                                 const int sa = dir ? 1 + i : 1 + 2 * i, sb2 = dir ? 3 + i : 2 + 2 * i;
-                                predict_blk_b(l, dir ? 15 : 14, dir ? 4 * i : 8 * i, 2, px, py);           // width 2 for both shapes, as the reference has it
+                                predict_blk_b(l, dir ? D_8x16 : D_16x8, dir ? 4 * i : 8 * i, 2, px, py);           // width 2 for both shapes, as the reference has it
                                 WAVE_SYNC();
                                 if (lane < 4) s.mvc[lane >> 1][lane & 1] = (i16)sb.me[l][lane >> 1 ? sb2 : sa][lane & 1];
                                 WAVE_SYNC();
@@ -554,7 +531,7 @@
                         total += Q.lambda * (int)((0x999757775ull >> (4 * (ty - T_B_L0_L0))) & 15);     // i_mb_b16x8_cost_table[B_L0_L0 ..]: 5 7 7 7 5 7 9 9 9
                         if (dir) { type8x16 = ty; cost8x16bi = total; part8x16_0 = pt0; part8x16_1 = pt1; }
                         else { type16x8 = ty; cost16x8bi = total; part16x8_0 = pt0; part16x8_1 = pt1; }
-                        if (total < i_cost_b) { i_cost_b = total; i_type_b = ty; i_part_b = dir ? 15 : 14; }
+                        if (total < i_cost_b) { i_cost_b = total; i_type_b = ty; i_part_b = dir ? D_8x16 : D_16x8; }
                     }
                 }
             }
@@ -567,12 +544,12 @@
                 for (int j = 0; j < 8; j++) {
                     const int l = j & 1, i = j >> 1;
                     int slot, w, h, bx, by, ptype, tc = 0;
-                    if (i_part_b == 16) {
+                    if (i_part_b == D_16x16) {
                         if (i) continue;
                         slot = 0; w = 16; h = 16; bx = 0; by = 0; tc = Q.lambda * 3;
-                        ptype = i_type_b == T_B_L0_L0 ? 3 : i_type_b == T_B_L1_L1 ? 7 : i_type_b == T_B_BI_BI ? 11 : 12;
-                    } else if (i_part_b == 14) { if (i > 1) continue; slot = 5 + i; w = 16; h = 8; bx = 0; by = 8 * i; ptype = i ? part16x8_1 : part16x8_0; }
-                    else if (i_part_b == 15) { if (i > 1) continue; slot = 7 + i; w = 8; h = 16; bx = 8 * i; by = 0; ptype = i ? part8x16_1 : part8x16_0; }
+                        ptype = i_type_b == T_B_L0_L0 ? D_L0_8x8 : i_type_b == T_B_L1_L1 ? D_L1_8x8 : i_type_b == T_B_BI_BI ? D_BI_8x8 : D_DIRECT_8x8;
+                    } else if (i_part_b == D_16x8) { if (i > 1) continue; slot = 5 + i; w = 16; h = 8; bx = 0; by = 8 * i; ptype = i ? part16x8_1 : part16x8_0; }
+                    else if (i_part_b == D_8x16) { if (i > 1) continue; slot = 7 + i; w = 8; h = 16; bx = 8 * i; by = 0; ptype = i ? part8x16_1 : part8x16_0; }
                     else { slot = 1 + i; w = 8; h = 8; bx = 8 * (i & 1); by = 8 * (i >> 1); ptype = SUB(i); tc = Q.lambda * 3; }
                     if (!sub_uses(ptype, l)) continue;
                     int vx = ME(l, slot, 0), vy = ME(l, slot, 1);
@@ -584,8 +561,8 @@
                     WAVE_SYNC();
                     if (lane < 3) sb.me[l][slot][lane] = lane == 0 ? vx : lane == 1 ? vy : nc;
                     WAVE_SYNC();
-                    if (i_part_b == 16 && ptype != 11) i_cost_b = nc + tc;
-                    if (i_part_b == 13 && ptype != 11) cost8bi += nc + tc - old;
+                    if (i_part_b == D_16x16 && ptype != D_BI_8x8) i_cost_b = nc + tc;
+                    if (i_part_b == D_8x8 && ptype != D_BI_8x8) cost8bi += nc + tc - old;
                 }
                 bstep = BS_SELECT;
                 continue;
@@ -595,14 +572,14 @@
             continue;
         } else if (bstep == BS_SELECT) {
             if (mbrd) {
-                i_type_b = T_B_SKIP; i_cost_b = bskip_cost; i_part_b = 16;
+                i_type_b = T_B_SKIP; i_cost_b = bskip_cost; i_part_b = D_16x16;
                 if (rd_l0 < i_cost_b) { i_cost_b = rd_l0; i_type_b = T_B_L0_L0; }
                 if (rd_l1 < i_cost_b) { i_cost_b = rd_l1; i_type_b = T_B_L1_L1; }
                 if (rd_bi < i_cost_b) { i_cost_b = rd_bi; i_type_b = T_B_BI_BI; }
                 if (rd_direct < i_cost_b) { i_cost_b = rd_direct; i_type_b = T_B_DIRECT; }
-                if (rd_168 < i_cost_b) { i_cost_b = rd_168; i_type_b = type16x8; i_part_b = 14; }
-                if (rd_816 < i_cost_b) { i_cost_b = rd_816; i_type_b = type8x16; i_part_b = 15; }
-                if (rd_8 < i_cost_b) { i_cost_b = rd_8; i_type_b = T_B_8x8; i_part_b = 13; }
+                if (rd_168 < i_cost_b) { i_cost_b = rd_168; i_type_b = type16x8; i_part_b = D_16x8; }
+                if (rd_816 < i_cost_b) { i_cost_b = rd_816; i_type_b = type8x16; i_part_b = D_8x16; }
+                if (rd_8 < i_cost_b) { i_cost_b = rd_8; i_type_b = T_B_8x8; i_part_b = D_8x8; }
                 type = i_type_b; part = i_part_b;
             }
             analyse_intra(i_satd_inter_b);                      // without the RD levels the reference passes 0 here (its i_satd_inter is only set for them): only I_16x16 gets a cost
@@ -630,9 +607,9 @@
             skip_mc = 0;
             // x264_refine_bidir (subme >= 5): the bi-predicted blocks of the chosen partition
             if (!IS_INTRA_T(type) && a.subme >= 5) {
-                if (part == 16) { if (type == T_B_BI_BI) refine_bidir_satd(0, 0, 0, 16, 16); }
-                else if (part == 14) { if (part16x8_0 == 11) refine_bidir_satd(5, 0, 0, 16, 8); if (part16x8_1 == 11) refine_bidir_satd(6, 0, 8, 16, 8); }
-                else if (part == 15) { if (part8x16_0 == 11) refine_bidir_satd(7, 0, 0, 8, 16); if (part8x16_1 == 11) refine_bidir_satd(8, 8, 0, 8, 16); }
+                if (part == D_16x16) { if (type == T_B_BI_BI) refine_bidir_satd(0, 0, 0, 16, 16); }
+                else if (part == D_16x8) { if (part16x8_0 == D_BI_8x8) refine_bidir_satd(5, 0, 0, 16, 8); if (part16x8_1 == D_BI_8x8) refine_bidir_satd(6, 0, 8, 16, 8); }
+                else if (part == D_8x16) { if (part8x16_0 == D_BI_8x8) refine_bidir_satd(7, 0, 0, 8, 16); if (part8x16_1 == D_BI_8x8) refine_bidir_satd(8, 8, 0, 8, 16); }
                 else if (type == T_B_8x8) for (int i = 0; i < 4; i++) if (SUB(i) == 11) refine_bidir_satd(1 + i, 8 * (i & 1), 8 * (i >> 1), 8, 8);
             }
         }

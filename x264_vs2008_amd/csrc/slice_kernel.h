@@ -35,6 +35,7 @@
 #include "me_exact.h"
 #include "intra_pred.h"
 #include "frame_internal.h"
+#include "mb_vocab.h"
 #include "trellis_wave.h"
 
 using namespace x264hip;
@@ -60,11 +61,7 @@ using namespace x264hip;
 #define FDU (19 * FD)
 #define FDV (19 * FD + 16)
 
-enum { T_I_4x4 = 0, T_I_8x8 = 1, T_I_16x16 = 2, T_I_PCM = 3, T_P_L0 = 4, T_P_8x8 = 5, T_P_SKIP = 6,
-       T_B_DIRECT = 7, T_B_L0_L0 = 8, T_B_L1_L1 = 12, T_B_BI_BI = 16, T_B_8x8 = 17, T_B_SKIP = 18 };
-#define IS_SKIP_T(t) ((t) == T_P_SKIP || (t) == T_B_SKIP)
 enum { NB_LEFT = 1, NB_TOP = 2, NB_TOPRIGHT = 4, NB_TOPLEFT = 8 };
-#define IS_INTRA_T(t) ((t) >= 0 && (t) <= T_I_PCM)
 
 struct SwRefs {
     const u8 *y[SW_MAX_REFS][4];
@@ -265,7 +262,6 @@ __device__ __forceinline__ int sw_decimate(const i16 *lv, int n)
     return score;
 }
 __device__ __forceinline__ int sw_ue_size(int v) { return v == 0 ? 1 : v < 3 ? 3 : 5; }   // bs_size_ue for 0..6
-__device__ __forceinline__ int sw_median(int a, int b, int c) { int mx = max(a, b), mn = min(a, b); return c > mx ? mx : c < mn ? mn : c; }
 
 // ---- motion compensation of one 16x16 vector into s.fd (x264_mb_mc_0xywh, R/common/macroblock.c:462-476)
 __device__ __forceinline__ void sw_mc16(SwLds &s, const SwRefs &refs, const SwArgs &a, int ri, int mvx, int mvy, ptrdiff_t oy, ptrdiff_t oc,
@@ -1135,15 +1131,10 @@ __device__ __forceinline__ unsigned long long sw_modes4(int nb, int &n)
     if (nb & NB_TOP) { n = 4; return 0x730Aull; }
     n = 1; return 0xBull;
 }
-__device__ __forceinline__ int sw_scan8(int i) { int x, y; sw_blk_xy(i, x, y); return 4 + 1 * 8 + (x >> 2) + 8 * (y >> 2); }
-__device__ __forceinline__ int sw_fix4(int m) { return m < 0 ? -1 : m < 9 ? m : 2; }      // x264_mb_pred_mode4x4_fix
-// x264_mb_predict_intra4x4_mode (R/common/macroblock.h:423-434)
+// x264_mb_predict_intra4x4_mode on the sweep's mode cache
 __device__ __forceinline__ int sw_pred_i4mode(const SwLds &s, int idx)
 {
-    const int ma = sw_fix4(__builtin_amdgcn_readfirstlane((int)s.i4c[sw_scan8(idx) - 1]));
-    const int mb = sw_fix4(__builtin_amdgcn_readfirstlane((int)s.i4c[sw_scan8(idx) - 8]));
-    const int m = ma < mb ? ma : mb;
-    return m < 0 ? 2 : m;
+    return mb_pred_i4mode(__builtin_amdgcn_readfirstlane((int)s.i4c[mb_scan8_luma(idx) - 1]), __builtin_amdgcn_readfirstlane((int)s.i4c[mb_scan8_luma(idx) - 8]));
 }
 // SATD / SAD of a 4x4 block from one row of differences per lane (rows of a block in lanes l, l^1, l^2, l^3); pixel.c:187-212
 __device__ __forceinline__ int sw_cost4x4_rows(int d0, int d1, int d2, int d3, int satd, int lane)

@@ -127,7 +127,7 @@
                         WAVE_SYNC();
                     }
                     if (lane < 16) dst[(lane >> 2) * FD + (lane & 3)] = sf.pels[lane];
-                    if (lane == 0) { s.nnz[idx] = (u8)best_nnz; s.pred4[idx] = (signed char)best_mode; s.i4c[sw_scan8(idx)] = (signed char)best_mode; }
+                    if (lane == 0) { s.nnz[idx] = (u8)best_nnz; s.pred4[idx] = (signed char)best_mode; s.i4c[mb_scan8_luma(idx)] = (signed char)best_mode; }
                     WAVE_SYNC();
                 }
             } else if (type == T_I_8x8) {
@@ -184,19 +184,19 @@
                     if (lane < 8) dst[7 * FD + lane] = sf.pels[lane];
                     else if (lane < 15 && !(idx & 1)) dst[(lane - 8) * FD + 7] = sf.pels[lane];
                     if (lane == 0) { *(u32 *)(s.nnz + 4 * idx) = best_nnz; s.pred8[idx] = (signed char)best_mode; }
-                    if (lane < 4) s.i4c[sw_scan8(4 * idx) + (lane & 1) + 8 * (lane >> 1)] = (signed char)best_mode;
+                    if (lane < 4) s.i4c[mb_scan8_luma(4 * idx) + (lane & 1) + 8 * (lane >> 1)] = (signed char)best_mode;
                     WAVE_SYNC();
                 }
             }
             rf_kind = 9;
         } else if (rf_kind == 3) {
             // ---- x264_me_refine_qpel_rd on every partition of the winner, analyse.c:2412-2462 ----
-            const int rf_np = part == 16 ? 1 : part == 13 ? 4 : 2;
+            const int rf_np = part == D_16x16 ? 1 : part == D_8x8 ? 4 : 2;
             if (q_st == -1) {
                 // the references of the partitions into the motion cache (x264_macroblock_cache_ref; a P_8x8 macroblock: x264_analyse_update_cache)
-                if (part == 16) cache_set(0, 0, 4, 4, me16r, 0, 0, 0);
-                else if (part == 14) { cache_set(0, 0, 4, 2, pme(4, 4), 0, 0, 0); cache_set(0, 2, 4, 2, pme(5, 4), 0, 0, 0); }
-                else if (part == 15) { cache_set(0, 0, 2, 4, pme(6, 4), 0, 0, 0); cache_set(2, 0, 2, 4, pme(7, 4), 0, 0, 0); }
+                if (part == D_16x16) cache_set(0, 0, 4, 4, me16r, 0, 0, 0);
+                else if (part == D_16x8) { cache_set(0, 0, 4, 2, pme(4, 4), 0, 0, 0); cache_set(0, 2, 4, 2, pme(5, 4), 0, 0, 0); }
+                else if (part == D_8x16) { cache_set(0, 0, 2, 4, pme(6, 4), 0, 0, 0); cache_set(2, 0, 2, 4, pme(7, 4), 0, 0, 0); }
                 else for (int i = 0; i < 4; i++) cache_set(2 * (i & 1), 2 * (i >> 1), 2, 2, pme(i, 4), pme(i, 0), pme(i, 1), 1);
                 update_cache_p();
                 q_st = 0;
@@ -226,11 +226,11 @@
             bool have = false;                                       // a candidate (q_cx, q_cy, q_tag) is to be priced
             while (!have && rf_kind == 3) {
                 if (q_st == 0) {                                     // a partition starts: COST_MV_SATD( bmx, bmy, bsatd, 0 ); COST_MV_RD( bmx, bmy, 0, 0, 0 )
-                    q_slot = part == 13 ? rf_i : part == 14 ? 4 + rf_i : part == 15 ? 6 + rf_i : -1;
-                    q_pix = part == 16 ? 0 : part == 14 ? 1 : part == 15 ? 2 : 3;
-                    q_w = part == 16 || part == 14 ? 16 : 8; q_h = part == 16 || part == 15 ? 16 : 8;
-                    q_bx = part == 13 ? 8 * (rf_i & 1) : part == 15 ? 8 * rf_i : 0; q_by = part == 13 ? 8 * (rf_i >> 1) : part == 14 ? 8 * rf_i : 0;
-                    q_i4 = part == 13 ? 4 * rf_i : part == 14 ? 8 * rf_i : part == 15 ? 4 * rf_i : 0;
+                    q_slot = part == D_8x8 ? rf_i : part == D_16x8 ? 4 + rf_i : part == D_8x16 ? 6 + rf_i : -1;
+                    q_pix = part == D_16x16 ? 0 : part == D_16x8 ? 1 : part == D_8x16 ? 2 : 3;
+                    q_w = part == D_16x16 || part == D_16x8 ? 16 : 8; q_h = part == D_16x16 || part == D_8x16 ? 16 : 8;
+                    q_bx = part == D_8x8 ? 8 * (rf_i & 1) : part == D_8x16 ? 8 * rf_i : 0; q_by = part == D_8x8 ? 8 * (rf_i >> 1) : part == D_16x8 ? 8 * rf_i : 0;
+                    q_i4 = part == D_8x8 ? 4 * rf_i : part == D_16x8 ? 8 * rf_i : part == D_8x16 ? 4 * rf_i : 0;
                     if (q_slot < 0) { q_bmx = me16x; q_bmy = me16y; q_ref = me16r; q_mvpx = bmvpx; q_mvpy = bmvpy; rf_best = (unsigned long long)(u32)rd16; }
                     else { q_bmx = pme(q_slot, 0); q_bmy = pme(q_slot, 1); q_ref = pme(q_slot, 4); q_mvpx = pme(q_slot, 6); q_mvpy = pme(q_slot, 7); rf_best = ~0ull >> 4; }
                     if (q_pix != 0 && q_i4 != 0) predict_blk(part, q_i4, q_w >> 2, q_mvpx, q_mvpy);

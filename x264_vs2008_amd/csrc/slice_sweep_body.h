@@ -231,8 +231,8 @@
             WAVE_SYNC();
         }
 
-        int type = T_I_16x16, mvx = 0, mvy = 0, ref = 0, skip_mc = 0, pred16 = 0, predc = 0, part = 16;
-        int sub_t_mb = 3;                    // lanes 0..3: h->mb.i_sub_partition[] (D_L0_4x4 0, 8x4 1, 4x8 2, 8x8 3)
+        int type = T_I_16x16, mvx = 0, mvy = 0, ref = 0, skip_mc = 0, pred16 = 0, predc = 0, part = D_16x16;
+        int sub_t_mb = D_L0_8x8;                    // lanes 0..3: h->mb.i_sub_partition[] (D_L0_4x4 0, 8x4 1, 4x8 2, 8x8 3)
         int satd_i16 = MX_COST_MAX, satd_chroma = MX_COST_MAX, pskx = 0, psky = 0;
         int satd_i8 = MX_COST_MAX, satd_i4 = MX_COST_MAX, i8_cbp = 0, i4_cbp = 0, t8 = 0, fi_open = 0, stat_alt = -1;
         if (a.flags_intra & 3) {
@@ -352,7 +352,7 @@
                                 for (int x = 0; x < 8; x++) sd += iabs(d[x]);
                                 c = half_sum8(sd);
                             }
-                            key = ((u32)(c + Q.lambda * (pm == sw_fix4(mode) ? 1 : 4)) << 4) | (u32)g;
+                            key = ((u32)(c + Q.lambda * (pm == mb_fix4(mode) ? 1 : 4)) << 4) | (u32)g;
                             if constexpr (RF) { if (r == 0) sf.i8dir[mode][idx] = (int)(key >> 4); }
                         }
                         // the reference's in-order strict '<' over the modes = the smallest (cost, slot) key
@@ -368,7 +368,7 @@
                         if (a.lossless && bmode < 2) v = sw_ll_px(s, 0, bmode, bx + (lane & 7), by + (lane >> 3));
                         WAVE_SYNC();
                         s.fd[FDY + (by + (lane >> 3)) * FD + bx + (lane & 7)] = (u8)v;
-                        if (lane < 4) s.i4c[sw_scan8(4 * idx) + (lane & 1) + 8 * (lane >> 1)] = (signed char)bmode;
+                        if (lane < 4) s.i4c[mb_scan8_luma(4 * idx) + (lane & 1) + 8 * (lane >> 1)] = (signed char)bmode;
                         WAVE_SYNC();
                     }
                     sw_encode_i8x8(s, a, Q, tq, idx, acbp, lane);
@@ -412,7 +412,7 @@
                                 d2 = (int)((fw >> 16) & 255) - sw_ll_px(s, 0, mode, bx + 2, by + r); d3 = (int)(fw >> 24) - sw_ll_px(s, 0, mode, bx + 3, by + r);
                             }
                             const int c = sw_cost4x4_rows(d0, d1, d2, d3, satd, lane);
-                            key = ((u32)(c + Q.lambda * (pm == sw_fix4(mode) ? 1 : 4)) << 4) | (u32)g;
+                            key = ((u32)(c + Q.lambda * (pm == mb_fix4(mode) ? 1 : 4)) << 4) | (u32)g;
                         }
                     }
                     u32 kb = (u32)__builtin_amdgcn_readlane((int)key, 0);
@@ -424,7 +424,7 @@
                     if (cost > thresh || idx == 15) break;
                     if (lane < 16) dst[(lane >> 2) * FD + (lane & 3)] = a.lossless && bmode < 2 ? (u8)sw_ll_px(s, 0, bmode, bx + (lane & 3), by + (lane >> 2))
                                                                          : s.pt4[(s.p4lut[bmode * 4 + (lane >> 2)] >> (8 * (lane & 3))) & 255];
-                    if (lane == 0) s.i4c[sw_scan8(idx)] = (signed char)bmode;
+                    if (lane == 0) s.i4c[mb_scan8_luma(idx)] = (signed char)bmode;
                     WAVE_SYNC();
                     sw_encode_i4x4(s, a, Q, tq, idx, acbp, lane);
                 }
@@ -475,7 +475,7 @@
                 // analysis already encoded all blocks but the last: take its state and finish; without it (trellis 1, --nr,
                 // lossless) every block is predicted and coded again.
                 const bool i8 = type == T_I_8x8;
-                if (lane < 16) s.i4c[sw_scan8(lane)] = i8 ? s.pred8[lane >> 2] : s.pred4[lane];
+                if (lane < 16) s.i4c[mb_scan8_luma(lane)] = i8 ? s.pred8[lane >> 2] : s.pred4[lane];
                 analyse_chroma();
                 if (skip_intra) {
                     *(u32 *)(s.fd + FDY + (lane >> 2) * FD + (lane & 3) * 4) = *(const u32 *)((i8 ? s.i8_fdec : s.i4_fdec) + lane * 4);
@@ -525,7 +525,7 @@
                 if constexpr (!BS) sw_mc_parts(s, refs, a, oy, oc, by_, bc_, lane, RF, mbx, mby);    // (B slice: the caller has run the bi-predictive motion compensation)
                 WAVE_SYNC();
                 // x264_mb_transform_8x8_allowed: a P_8x8 macroblock only with four 8x8 sub-partitions
-                if (!mbrd && a.transform8x8 && !a.lossless && (type != T_P_8x8 || __ballot(lane < 4 && sub_t_mb != 3) == 0)) {
+                if (!mbrd && a.transform8x8 && !a.lossless && (type != T_P_8x8 || __ballot(lane < 4 && sub_t_mb != D_L0_8x8) == 0)) {
                     // x264_mb_analyse_transform (R/encoder/analyse.c:2109-2126): SA8D against SATD of the 16x16 prediction error
                     int raw = 0;
                     if (lane < 32) {
@@ -544,7 +544,7 @@
                 } else
                 cbp_luma = t8 ? sw_encode_inter_luma8(s, a, Q, tq, lane, &nr_acc8, nr_on) : sw_encode_inter_luma(s, a, Q, tq, lane, &nr_acc4, nr_on);   // never a conditional pointer: that pins the counter in scratch memory
                 cbp_chroma = sw_encode_chroma(s, a, Q, tq, 1, lane);
-                if (type == T_P_L0 && part == 16 && !(cbp_luma | cbp_chroma) && mvx == pskx && mvy == psky && ref == 0) type = T_P_SKIP;
+                if (type == T_P_L0 && part == D_16x16 && !(cbp_luma | cbp_chroma) && mvx == pskx && mvy == psky && ref == 0) type = T_P_SKIP;
                 if (BS && type == T_B_DIRECT && !(cbp_luma | cbp_chroma)) type = T_B_SKIP;       // macroblock.c:784-788
             }
         };
@@ -614,7 +614,7 @@
             MbSynDev y;
             y.slice_type = a.slice_type; y.type = type; y.partition = part; y.i16mode = pred16; y.chroma_mode = predc;
             y.cbp_luma = cbp_luma; y.cbp_chroma = cbp_chroma; y.t8 = t8; y.qp = Q.qp; y.n_ref = a.n_refs; y.pps_t8 = a.transform8x8;
-            y.t8_allowed = a.transform8x8 && (type == T_P_L0 || (type == T_P_8x8 && __ballot(lane < 4 && sub_t_mb != 3) == 0));
+            y.t8_allowed = a.transform8x8 && (type == T_P_L0 || (type == T_P_8x8 && __ballot(lane < 4 && sub_t_mb != D_L0_8x8) == 0));
             if constexpr (BS) y.t8_allowed = a.transform8x8 && type >= T_B_DIRECT && type <= T_B_8x8;
             // h->mb.type[] holds x264_mb_type_fix'ed types (I_8x8 is stored as I_4x4, R/common/macroblock.c:1209,1226)
             y.type_left = left_type == T_I_8x8 ? T_I_4x4 : left_type; y.type_top = type_top == T_I_8x8 ? T_I_4x4 : type_top; y.cbp_left = left_cbp; y.cbp_top = cbp_top; y.cpm_left = left_cpm; y.cpm_top = cpm_top;
@@ -657,7 +657,7 @@
             // the register file as lane-indexed arrays: entry k = lane k of a VGPR, read with v_readlane (uniform index), written
             // by the lane itself or with v_writelane -- no LDS round trip, no barrier.
             int cref_v = -2, cmvx_v = 0, cmvy_v = 0, pme_v = 0;
-            int sub_mx = 0, sub_my = 0, sub_cost = 0, sub_px = 0, sub_py = 0, sub_t = 3;      // sub-8x8 records (lanes 0..31) and chosen type (lanes 0..3)
+            int sub_mx = 0, sub_my = 0, sub_cost = 0, sub_px = 0, sub_py = 0, sub_t = D_L0_8x8;      // sub-8x8 records (lanes 0..31) and chosen type (lanes 0..3)
             if (is_p && (RD || (a.flags_inter & 0x10))) {
                 // the full motion cache for x264_mb_predict_mv on partitions: -2 = not available, neighbours as cache_load leaves them
                 if ((nb & NB_TOP) && lane >= 4 && lane < 8) {
@@ -684,13 +684,15 @@
                     WAVE_SYNC();
                 }
             }
-            // x264_mb_predict_mv_16x16, :90-128
+            // x264_mb_predict_mv_16x16, :90-128, and below x264_mb_predict_mv on the cache held in registers: the P flow keeps its own copies of
+            // mb_vocab.h's mb_predict_mv_abc / mb_predict_mv (the shared statements, which these restate) -- routed through them, the RD
+            // instantiation spills (3 VGPR spills, 8 bytes of scratch where it has none)
             auto predict16 = [&](int i_ref, int &px, int &py) {
                 const int cnt = (ra == i_ref) + (rb == i_ref) + (rc == i_ref);
-                if (cnt > 1) { px = sw_median(ax, bx, cx); py = sw_median(ay, byv, cy); }
+                if (cnt > 1) { px = mb_median(ax, bx, cx); py = mb_median(ay, byv, cy); }
                 else if (cnt == 1) { if (ra == i_ref) { px = ax; py = ay; } else if (rb == i_ref) { px = bx; py = byv; } else { px = cx; py = cy; } }
                 else if (rb == -2 && rc == -2 && ra != -2) { px = ax; py = ay; }
-                else { px = sw_median(ax, bx, cx); py = sw_median(ay, byv, cy); }
+                else { px = mb_median(ax, bx, cx); py = mb_median(ay, byv, cy); }
             };
             // x264_mb_predict_mv_pskip, :131-149
             if (ra == -2 || rb == -2 || !(ra | ax | ay) || !(rb | bx | byv)) { pskx = 0; psky = 0; }
@@ -796,28 +798,28 @@
                     };
                     // x264_mb_predict_mv (R/common/macroblock.c:28-88) from the cache; cur_part = h->mb.i_partition
                     auto predict_blk = [&](int cur_part, int idx, int width, int &px, int &py) {
-                        const int i8 = sw_scan8(idx), i_ref = __builtin_amdgcn_readlane(cref_v, i8);
+                        const int i8 = mb_scan8_luma(idx), i_ref = __builtin_amdgcn_readlane(cref_v, i8);
                         int ra = __builtin_amdgcn_readlane(cref_v, i8 - 1), rb = __builtin_amdgcn_readlane(cref_v, i8 - 8), rc = __builtin_amdgcn_readlane(cref_v, i8 - 8 + width), kc = i8 - 8 + width;
                         if ((idx & 3) == 3 || (width == 2 && (idx & 3) == 2) || rc == -2) { kc = i8 - 8 - 1; rc = __builtin_amdgcn_readlane(cref_v, kc); }
                         const int ax = __builtin_amdgcn_readlane(cmvx_v, i8 - 1), ay = __builtin_amdgcn_readlane(cmvy_v, i8 - 1), bx = __builtin_amdgcn_readlane(cmvx_v, i8 - 8), byv = __builtin_amdgcn_readlane(cmvy_v, i8 - 8);
                         const int cx = __builtin_amdgcn_readlane(cmvx_v, kc), cy = __builtin_amdgcn_readlane(cmvy_v, kc);
-                        if (cur_part == 14) {                       // D_16x8
+                        if (cur_part == D_16x8) {
                             if (idx == 0 && rb == i_ref) { px = bx; py = byv; return; }
                             if (idx != 0 && ra == i_ref) { px = ax; py = ay; return; }
-                        } else if (cur_part == 15) {                // D_8x16
+                        } else if (cur_part == D_8x16) {
                             if (idx == 0 && ra == i_ref) { px = ax; py = ay; return; }
                             if (idx != 0 && rc == i_ref) { px = cx; py = cy; return; }
                         }
                         const int cnt = (ra == i_ref) + (rb == i_ref) + (rc == i_ref);
-                        if (cnt > 1) { px = sw_median(ax, bx, cx); py = sw_median(ay, byv, cy); }
+                        if (cnt > 1) { px = mb_median(ax, bx, cx); py = mb_median(ay, byv, cy); }
                         else if (cnt == 1) { if (ra == i_ref) { px = ax; py = ay; } else if (rb == i_ref) { px = bx; py = byv; } else { px = cx; py = cy; } }
                         else if (rb == -2 && rc == -2 && ra != -2) { px = ax; py = ay; }
-                        else { px = sw_median(ax, bx, cx); py = sw_median(ay, byv, cy); }
+                        else { px = mb_median(ax, bx, cx); py = mb_median(ay, byv, cy); }
                     };
                     int i_cost = best;
                     int c8x8 = MX_COST_MAX, c16x8 = MX_COST_MAX, c8x16 = MX_COST_MAX;   // a->l0.i_cost8x8 / i_cost16x8 / i_cost8x16
                     auto search_partitions = [&]() {
-                    part = 16;                                       // D_16x16
+                    part = D_16x16;
                     if (a.flags_inter & 0x10) {
                         // ---- X264_ANALYSE_PSUB16x16: p8x8, then p16x8 / p8x16 (R/encoder/analyse.c:2222-2265) ----
                         cache_set(0, 0, 4, 4, ref, 0, 0, 0);
@@ -902,7 +904,7 @@
                             cost8x8 = pme(0, 2) + pme(1, 2) + pme(2, 2) + pme(3, 2);
                             if (a.cabac) cost8x8 -= ref_cost;
                         }
-                        if (cost8x8 < best) { type = T_P_8x8; part = 13; i_cost = cost8x8; }
+                        if (cost8x8 < best) { type = T_P_8x8; part = D_8x8; i_cost = cost8x8; }
                         if ((a.flags_inter & 0x20) && type == T_P_8x8) {
                             // ---- X264_ANALYSE_PSUB8x8 (R/encoder/analyse.c:2252-2277): p4x4, and only if that beats the 8x8 block, p8x4 and p4x8
                             // (:1407-1519).  Records (mv, cost, mvp) of me4x4[i][k] / me8x4[i][k] / me4x8[i][k] sit in lanes 4i+k / 16+2i+k / 24+2i+k.
@@ -910,7 +912,7 @@
                             mo_sub.chroma_me = 0;                        // b_chroma_me && i_pixel <= PIXEL_8x8, me.c:654
                             for (int i = 0; i < 4; i++) {
                                 const int r = pme(i, 4), x0 = 2 * (i & 1), y0 = 2 * (i >> 1);
-                                int c8 = 0, subt = 3;
+                                int c8 = 0, subt = D_L0_8x8;
                                 for (int t = 0; t < 3; t++) {
                                     const int sw = t == 1 ? 2 : 1, sh = t == 2 ? 2 : 1, sn = t == 0 ? 4 : 2, rec0 = t == 0 ? 4 * i : t == 1 ? 16 + 2 * i : 24 + 2 * i;
                                     const int cvx = t == 0 ? pme(i, 0) : __builtin_amdgcn_readlane(sub_mx, 4 * i), cvy = t == 0 ? pme(i, 1) : __builtin_amdgcn_readlane(sub_my, 4 * i);
@@ -935,16 +937,16 @@
                                     if (a.chroma_me && a.subme >= 5) cst += sw_sub_chroma(s, refs, a, r, i, t, rec0, sub_mx, sub_my, satd, oc, bc_, lane);
                                     if (t == 0) {
                                         if (!(cst < pme(i, 2))) break;
-                                        c8 = cst; subt = 0;
+                                        c8 = cst; subt = D_L0_4x4;
                                     } else if (cst < c8) { c8 = cst; subt = t; }
                                 }
-                                if (subt != 3) i_cost += c8 - pme(i, 2);
+                                if (subt != D_L0_8x8) i_cost += c8 - pme(i, 2);
                                 // x264_mb_cache_mv_p8x8
-                                if (subt == 3) cache_set(x0, y0, 2, 2, r, pme(i, 0), pme(i, 1), 1);
+                                if (subt == D_L0_8x8) cache_set(x0, y0, 2, 2, r, pme(i, 0), pme(i, 1), 1);
                                 else {
-                                    const int sw = subt == 1 ? 2 : 1, sh = subt == 2 ? 2 : 1, sn = subt == 0 ? 4 : 2, rec0 = subt == 0 ? 4 * i : subt == 1 ? 16 + 2 * i : 24 + 2 * i;
+                                    const int sw = subt == D_L0_8x4 ? 2 : 1, sh = subt == D_L0_4x8 ? 2 : 1, sn = subt == D_L0_4x4 ? 4 : 2, rec0 = subt == D_L0_4x4 ? 4 * i : subt == D_L0_8x4 ? 16 + 2 * i : 24 + 2 * i;
                                     for (int k = 0; k < sn; k++)
-                                        cache_set(x0 + (subt == 0 ? (k & 1) : subt == 2 ? k : 0), y0 + (subt == 0 ? (k >> 1) : subt == 1 ? k : 0), sw, sh, r,
+                                        cache_set(x0 + (subt == D_L0_4x4 ? (k & 1) : subt == D_L0_4x8 ? k : 0), y0 + (subt == D_L0_4x4 ? (k >> 1) : subt == D_L0_8x4 ? k : 0), sw, sh, r,
                                                   __builtin_amdgcn_readlane(sub_mx, rec0 + k), __builtin_amdgcn_readlane(sub_my, rec0 + k), 1);
                                 }
                                 if (lane == i) sub_t = subt;
@@ -967,7 +969,7 @@
                                         }
                                         if (dir) cache_set(2 * i, 0, 2, 4, r, 0, 0, 0); else cache_set(0, 2 * i, 4, 2, r, 0, 0, 0);
                                         int px, py, vx, vy, cm;
-                                        predict_blk(dir ? 15 : 14, dir ? 4 * i : 8 * i, dir ? 2 : 4, px, py);
+                                        predict_blk(dir ? D_8x16 : D_16x8, dir ? 4 * i : 8 * i, dir ? 2 : 4, px, py);
                                         aim(r, dir ? 8 : 16, dir ? 16 : 8, dir ? 8 * i : 0, dir ? 0 : 8 * i);
                                         c.mvpx = px; c.mvpy = py;
                                         LAUNDER(); c.lane = lane;
@@ -979,14 +981,14 @@
                                     sum += bcost;
                                 }
                                 if (dir) c8x16 = sum; else c16x8 = sum;
-                                if (sum < i_cost) { i_cost = sum; type = T_P_L0; part = dir ? 15 : 14; }
+                                if (sum < i_cost) { i_cost = sum; type = T_P_L0; part = dir ? D_8x16 : D_16x8; }
                             }
                         c8x8 = cost8x8;
                     }
                     };
                     // x264_me_refine_qpel on the winning partition (analyse.c:2289-2352); the reference cost leaves every block's sum (me.c:639-640)
                     auto refine_winner = [&]() {
-                    if (part == 16) {
+                    if (part == D_16x16) {
                         aim(ref, 16, 16, 0, 0);
                         c.mvpx = bmvpx; c.mvpy = bmvpy;
                         best -= (Q.lambda * refs.ref_bits[ref]);
@@ -997,22 +999,22 @@
                         if (lane < 4) s.ref8[lane] = (signed char)ref;
                     } else {
                         i_cost = 0;
-                        const int nblk = part == 13 ? 4 : 2, slot0 = part == 13 ? 0 : part == 14 ? 4 : 6;
+                        const int nblk = part == D_8x8 ? 4 : 2, slot0 = part == D_8x8 ? 0 : part == D_16x8 ? 4 : 6;
                         for (int i = 0; i < nblk; i++) {
                             // an 8x8 block of a P_8x8 macroblock refines its sub-partitions (analyse.c:2317-2352): no reference cost in their
                             // sums and no chroma (me.c:639, :654)
-                            const int subt = part == 13 ? __builtin_amdgcn_readlane(sub_t, i) : 3, nj = subt == 3 ? 1 : subt == 0 ? 4 : 2;
+                            const int subt = part == D_8x8 ? __builtin_amdgcn_readlane(sub_t, i) : D_L0_8x8, nj = subt == D_L0_8x8 ? 1 : subt == D_L0_4x4 ? 4 : 2;
                             for (int k = 0; k < nj; k++) {
-                                int bx = part == 13 ? 8 * (i & 1) : part == 15 ? 8 * i : 0, by = part == 13 ? 8 * (i >> 1) : part == 14 ? 8 * i : 0;
-                                int w = part == 14 ? 16 : 8, h = part == 15 ? 16 : 8;
+                                int bx = part == D_8x8 ? 8 * (i & 1) : part == D_8x16 ? 8 * i : 0, by = part == D_8x8 ? 8 * (i >> 1) : part == D_16x8 ? 8 * i : 0;
+                                int w = part == D_16x8 ? 16 : 8, h = part == D_8x16 ? 16 : 8;
                                 const int r = pme(slot0 + i, 4);
                                 int vx = pme(slot0 + i, 0), vy = pme(slot0 + i, 1), cin = pme(slot0 + i, 2) - pme(slot0 + i, 5);
                                 MeOpts mo_r = mo;
                                 c.mvpx = pme(slot0 + i, 6); c.mvpy = pme(slot0 + i, 7);
-                                if (subt != 3) {
-                                    const int rec = (subt == 0 ? 4 * i : subt == 1 ? 16 + 2 * i : 24 + 2 * i) + k;
-                                    bx += 4 * (subt == 0 ? (k & 1) : subt == 2 ? k : 0); by += 4 * (subt == 0 ? (k >> 1) : subt == 1 ? k : 0);
-                                    w = subt == 1 ? 8 : 4; h = subt == 2 ? 8 : 4;
+                                if (subt != D_L0_8x8) {
+                                    const int rec = (subt == D_L0_4x4 ? 4 * i : subt == D_L0_8x4 ? 16 + 2 * i : 24 + 2 * i) + k;
+                                    bx += 4 * (subt == D_L0_4x4 ? (k & 1) : subt == D_L0_4x8 ? k : 0); by += 4 * (subt == D_L0_4x4 ? (k >> 1) : subt == D_L0_8x4 ? k : 0);
+                                    w = subt == D_L0_8x4 ? 8 : 4; h = subt == D_L0_4x8 ? 8 : 4;
                                     vx = __builtin_amdgcn_readlane(sub_mx, rec); vy = __builtin_amdgcn_readlane(sub_my, rec); cin = __builtin_amdgcn_readlane(sub_cost, rec);
                                     c.mvpx = __builtin_amdgcn_readlane(sub_px, rec); c.mvpy = __builtin_amdgcn_readlane(sub_py, rec);
                                     mo_r.chroma_me = 0;
@@ -1037,7 +1039,7 @@
                     search_partitions();
                     refine_winner();
                     WAVE_SYNC();
-                    if (part == 13) sub_t_mb = sub_t;
+                    if (part == D_8x8) sub_t_mb = sub_t;
                     PROF(2);
                     LAUNDER();
                     if (a.chroma_me) {
@@ -1086,10 +1088,10 @@
                         auto update_cache_p = [&]() {
                             if (type == T_P_SKIP) return;                        // encode_pskip sets the skip vector itself
                             const int bx4 = lane & 3, by4 = (lane >> 2) & 3, bx8 = lane & 1, by8 = (lane >> 1) & 1;
-                            const int slot = part == 14 ? 4 + (by4 >> 1) : part == 15 ? 6 + (bx4 >> 1) : (by4 >> 1) * 2 + (bx4 >> 1);
-                            const int slot8 = part == 14 ? 4 + by8 : part == 15 ? 6 + bx8 : by8 * 2 + bx8;
+                            const int slot = part == D_16x8 ? 4 + (by4 >> 1) : part == D_8x16 ? 6 + (bx4 >> 1) : (by4 >> 1) * 2 + (bx4 >> 1);
+                            const int slot8 = part == D_16x8 ? 4 + by8 : part == D_8x16 ? 6 + bx8 : by8 * 2 + bx8;
                             int vx = __shfl(pme_v, slot * 8 + 0, 64), vy = __shfl(pme_v, slot * 8 + 1, 64), vr = __shfl(pme_v, slot8 * 8 + 4, 64);
-                            if (part == 16) { vx = me16x; vy = me16y; vr = me16r; }
+                            if (part == D_16x16) { vx = me16x; vy = me16y; vr = me16r; }
                             if (lane < 16) { s.mv4[lane][0] = (i16)vx; s.mv4[lane][1] = (i16)vy; }
                             if (lane < 4) s.ref8[lane] = (signed char)vr;
                             {   // the motion cache's copy of block 12 (raster block 10, 8x8 block 3) follows the candidate
@@ -1106,7 +1108,7 @@
                                 if (!mbrd) continue;
                                 cache_fenc_satd();
                                 if (!is_p || !(me16r == 0 && me16x == pskx && me16y == psky)) continue;
-                                type = T_P_L0; part = 16;
+                                type = T_P_L0; part = D_16x16;
                             } else if (step == 1) {
                                 if (rd_skip) { step = 9; continue; }
                                 int intra_thresh = MX_COST_MAX;              // an I slice: x264_mb_analyse_intra(h, &analysis, COST_MAX), analyse.c:2175
@@ -1115,7 +1117,7 @@
                                     search_partitions();
                                     if (!mbrd) refine_winner();
                                     WAVE_SYNC();
-                                    if (part == 13) sub_t_mb = sub_t;
+                                    if (part == D_8x8) sub_t_mb = sub_t;
                                     PROF(2);
                                     LAUNDER();
                                     final_type = type; final_part = part;
@@ -1132,16 +1134,16 @@
                                 continue;
                             } else if (step == 2) {
                                 if (!(rd16 == MX_COST_MAX && best <= rd_isat * 3 / 2)) continue;
-                                part = 16;
+                                part = D_16x16;
                             } else if (step == 3) {
                                 if (!(c16x8 <= rd_thresh)) { c16x8 = MX_COST_MAX; continue; }
-                                part = 14;
+                                part = D_16x8;
                             } else if (step == 4) {
                                 if (!(c8x16 <= rd_thresh)) { c8x16 = MX_COST_MAX; continue; }
-                                part = 15;
+                                part = D_8x16;
                             } else if (step == 5) {
                                 if (!(c8x8 <= rd_thresh)) { c8x8 = MX_COST_MAX; continue; }
-                                type = T_P_8x8; part = 13;
+                                type = T_P_8x8; part = D_8x8;
                             } else if (step == 6) {
                                 final_type = T_P_L0; final_part = 16; i_cost = rd16;
                                 if (c16x8 < i_cost) { i_cost = c16x8; final_part = 14; }
@@ -1341,9 +1343,9 @@
             a.mv[((size_t)mb * 16 + lane) * 2 + 1] = (i16)(intra ? 0 : s.mv4[lane][1]);
             if ((lane & 3) == 3) { s.left_mv4[lane >> 2][0] = (i16)(intra ? 0 : s.mv4[lane][0]); s.left_mv4[lane >> 2][1] = (i16)(intra ? 0 : s.mv4[lane][1]); }
             const bool i48 = type == T_I_4x4 || type == T_I_8x8;
-            a.i4mode[(size_t)mb * 16 + lane] = i48 ? s.i4c[sw_scan8(lane)] : (signed char)2;
+            a.i4mode[(size_t)mb * 16 + lane] = i48 ? s.i4c[mb_scan8_luma(lane)] : (signed char)2;
             if (lane == 5 || lane == 7 || lane == 13 || lane == 15)       // what the next macroblock sees to its left
-                s.left_i4[lane == 5 ? 0 : lane == 7 ? 1 : lane == 13 ? 2 : 3] = i48 ? s.i4c[sw_scan8(lane)] : (signed char)2;
+                s.left_i4[lane == 5 ? 0 : lane == 7 ? 1 : lane == 13 ? 2 : 3] = i48 ? s.i4c[mb_scan8_luma(lane)] : (signed char)2;
         }
         if (lane < 4) {
             const signed char rv = (signed char)(is_p || BS ? (intra ? -1 : s.ref8[lane]) : -1);
@@ -1365,14 +1367,14 @@
             }
             if (lane == 0) {
                 const int sbp = type == T_B_SKIP || type == T_B_DIRECT ? 0xf
-                              : type == T_B_8x8 ? (sb.sub[0] == 12) | (sb.sub[1] == 12) << 1 | (sb.sub[2] == 12) << 2 | (sb.sub[3] == 12) << 3 : 0;
+                              : type == T_B_8x8 ? (sb.sub[0] == D_DIRECT_8x8) | (sb.sub[1] == D_DIRECT_8x8) << 1 | (sb.sub[2] == D_DIRECT_8x8) << 2 | (sb.sub[3] == D_DIRECT_8x8) << 3 : 0;
                 (rd.skipbp + cb)[mb] = (u8)sbp; sb.left_skipbp = (u8)sbp;
             }
         }
         if (lane == 0) {
             const int cbp_dc = a.cabac ? (s.nnz[24] | s.nnz[25] << 1 | s.nnz[26] << 2) : 0;
             a.mb_type[mb] = (signed char)type;
-            (a.partition + cb)[mb] = (signed char)(intra || IS_SKIP_T(type) || (BS && type == T_B_DIRECT) ? 16 : part);
+            (a.partition + cb)[mb] = (signed char)(intra || IS_SKIP_T(type) || (BS && type == T_B_DIRECT) ? D_16x16 : part);
             (a.i16mode + cb)[mb] = (signed char)(type == T_I_16x16 ? pred16 : 0);
             (a.chroma_mode + cb)[mb] = (signed char)(intra ? predc : 0);
             (a.qp_out + cb)[mb] = (signed char)mb_qp;
