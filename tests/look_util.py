@@ -37,7 +37,7 @@ class CpuLook:
         self.me_method, self.me_range, self.weightb, self.bias, self.bframes = min(1, me_method), me_range, weightb, bframe_bias, bframes
         self.frames = {}
         self.cost_mv = np.zeros(2 * SPAN + 1, np.int16)
-        lib.x264hip_cost_mv_table(C.c_int(1), C.c_int(SPAN), self.cost_mv.ctypes.data_as(C.c_void_p))    # a->i_lambda = x264_lambda_tab[12] = 1
+        lib.x264hip_cost_mv_table(1, SPAN, self.cost_mv.ctypes.data_as(C.c_void_p))    # a->i_lambda = x264_lambda_tab[12] = 1
 
     def add(self, number, y, u, v):
         g, pic = self.g, hostpic.HostPic(self.g)

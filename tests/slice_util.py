@@ -94,7 +94,7 @@ def run_chain2(hip_lib, cqm, size, frames, y, u, v, kw, ekw, batch=1):
                 n_mb = state.get("mb_type").shape[1]
                 for nm, tail, dt in (("mv1", (16, 2), np.int16), ("ref1", (4,), np.int8)):
                     a = np.zeros((batch, n_mb) + tail, dt)
-                    assert enc.ctx.lib.x264hip_memcpy_d2h(a.ctypes.data_as(C.c_void_p), C.c_void_p(getattr(state.st, nm)), C.c_size_t(a.nbytes)) == 0, "frame %d: copying %s from the device failed" % (f, nm)
+                    assert enc.ctx.lib.x264hip_memcpy_d2h(a.ctypes.data_as(C.c_void_p), getattr(state.st, nm), a.nbytes) == 0, "frame %d: copying %s from the device failed" % (f, nm)
                     if stype != sl.SLICE_B:               # the reference reports zeros / -1 outside B slices
                         a[...] = 0 if nm == "mv1" else -1
                     d[nm] = a

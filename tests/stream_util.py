@@ -74,8 +74,7 @@ def run_async(hip_lib, cs, launches=3, drift=2):
                              chroma_me=c.get("chroma_me", 1), trellis=c.get("trellis", 0), psy_rd=c.get("psy_rd", 0.0), aq_mode=c["aq"], aq_strength=1.0,
                              bframes=c["bframes"], weightb=c["weightb"], direct_pred=c.get("direct_pred", 1), qp_min=0)
     cap = min(1 << 16, enc.payload_cap - 64)          # (PAYLOAD_LEAD bytes of every chain's slot precede the payload)
-    hip_lib.x264hip_host_alloc.restype = C.c_void_p
-    pin = hip_lib.x264hip_host_alloc(C.c_size_t(len(cs) * frames * (cap + 64)))
+    pin = hip_lib.x264hip_host_alloc(len(cs) * frames * (cap + 64))
     recs = [[] for _ in cs]
 
     def fill(pic, f):
@@ -94,7 +93,7 @@ def run_async(hip_lib, cs, launches=3, drift=2):
     got = [[(f, st, qp, C.string_at(base + 64, C.c_int32.from_address(base).value)) for f, st, qp, base in r] for r in recs]
     sizes = list(enc.launch_sizes)
     enc.close()
-    hip_lib.x264hip_host_free(C.c_void_p(pin))
+    hip_lib.x264hip_host_free(pin)
     return got, sizes
 
 

@@ -1,7 +1,9 @@
 """CPU: the C-ABI library loads and exports every symbol include/*.h declares
 (no compute, no GPU), host-side helpers, and the N > 1 frame-sharding path on
 two gloo ranks."""
+import ast
 import ctypes as C
+import glob
 import os
 import re
 import subprocess
@@ -13,21 +15,34 @@ import pytest
 from paths import ROOT
 
 
-def _declared_functions(path):
-    src = open(path).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    src = re.sub(r"typedef\s+struct\s*\{.*?\}\s*\w+\s*;", "", src, flags=re.S)
-    names = re.findall(r"\b(x264(?:hip)?_\w+)\s*\(", src)
-    return sorted(set(n for n in names if not n.endswith("_t")))
+HEADERS = ("x264hip.h", "x264hip_lookahead.h", "x264hip_stream.h")
+RAW_TYPEDEFS = {"x264hip_frame_stat": 32}          # the typedef structs Python reads as raw bytes (stream.py, through numpy) and mirrors by no record: name -> sizeof
+STRUCT = r"typedef\s+struct\s*\w*\s*\{.*?\}\s*(\w+)\s*;"
 
 
-def _declared_non_int(path):
-    """The functions a header declares with a return type other than int / void."""
-    src = open(path).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    src = re.sub(r"typedef\s+struct\s*\{.*?\}\s*\w+\s*;", "", src, flags=re.S)
-    decls = re.findall(r"([\w \t\*]+?)\b(x264(?:hip)?_\w+)\s*\(", src)
-    return sorted(set(n for ret, n in decls if not n.endswith("_t") and " ".join(ret.split()) not in ("int", "void")))
+def _header(name):
+    with open(os.path.join(ROOT, "include", name)) as f:
+        return re.sub(r"/\*.*?\*/", "", f.read(), flags=re.S)
+
+
+def _class(decl, named):
+    """The class of a return type, or of a parameter written with its name (named), as abi.PROTOTYPES spells it: a * or [ makes a pointer,
+    anything else is int, size_t, float or (a return type) void.  Any other spelling is an error, not a guess."""
+    if "*" in decl or "[" in decl:
+        return "s" if not named and decl.replace("*", " * ").split() == ["const", "char", "*"] else "p"
+    words = decl.split()[:-1] if named else decl.split()
+    assert len(words) == 1 and words[0] in ("int", "size_t", "float") + (() if named else ("void",)), "no class for %r" % decl
+    return {"int": "i", "size_t": "z", "float": "f", "void": "v"}[words[0]]
+
+
+def _declarations(name):
+    """{function: "return:parameters"} of the functions a header declares, in the notation of abi.PROTOTYPES."""
+    src = re.sub(STRUCT, "", _header(name), flags=re.S)
+    out = {}
+    for ret, fn, params in re.findall(r"([\w \t\*]+?)\b(x264(?:hip)?_\w+)\s*\(([^;{()]*)\)\s*;", src):
+        assert fn not in out, fn
+        out[fn] = _class(ret, False) + ":" + "".join(_class(q, True) for q in params.split(",") if params.strip() != "void")
+    return out
 
 
 def test_library_exports_every_declared_symbol():
@@ -35,41 +50,95 @@ def test_library_exports_every_declared_symbol():
     if not os.path.exists(L.SO_PATH):
         L.build()
     lib = L.open_library()
-    for header in ("x264hip.h", "x264hip_lookahead.h", "x264hip_stream.h"):
-        declared = _declared_functions(os.path.join(ROOT, "include", header))
+    for header in HEADERS:
+        declared = sorted(_declarations(header))
         assert len(declared) > (30 if header == "x264hip.h" else 8)
         missing = [n for n in declared if not hasattr(lib, n)]
         assert not missing, "declared in include/%s but not exported: %s" % (header, missing)
-        # ctypes takes every function to return int: one that returns a pointer, a size_t or a float needs its restype declared by open_library()
-        other = _declared_non_int(os.path.join(ROOT, "include", header))
-        assert header != "x264hip.h" or len(other) > 10
-        default = [n for n in other if getattr(lib, n).restype is C.c_int]
-        assert not default, "declared in include/%s with a return type other than int / void, restype left at the default: %s" % (header, default)
 
 
-def test_lookahead_struct_sizes_match_header():
-    """The ctypes mirrors of the round-3 structures (x264_vs2008_amd/lookahead.py, stream.py) against the C headers."""
-    from x264_vs2008_amd import lookahead as LA
-    from x264_vs2008_amd import stream as ST
-    from x264_vs2008_amd import slice as SL
-    from x264_vs2008_amd import mux as MX
-    prog = r'''
-#include <stdio.h>
-#include "x264hip_lookahead.h"
-#include "x264hip_stream.h"
-int main(void){ printf("%zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu\n", sizeof(x264hip_lookahead_params), sizeof(x264hip_look_need), sizeof(x264hip_look_frame),
- sizeof(x264hip_look_slot), sizeof(x264hip_look_task), sizeof(x264hip_look_params), sizeof(x264hip_chain_sweep), sizeof(x264hip_cavlc_params),
- sizeof(x264hip_encoder_params), sizeof(x264hip_slice_header), sizeof(x264hip_frame_stat)); return 0; }
-'''
-    exe = os.path.join(ROOT, "tests", "_sizes2.bin")
-    subprocess.run(["gcc", "-x", "c", "-", "-I", os.path.join(ROOT, "include"), "-o", exe], input=prog.encode(), check=True)
-    try:
-        got = [int(v) for v in subprocess.check_output([exe]).split()]
-    finally:
-        os.remove(exe)
-    want = [C.sizeof(LA.LookaheadParams), C.sizeof(LA.Need), C.sizeof(LA.Frame), C.sizeof(LA.LookSlot), C.sizeof(LA.LookTask), C.sizeof(LA.LookParams),
-            C.sizeof(ST.ChainSweep), C.sizeof(SL.CavlcParams), C.sizeof(MX.EncoderParams), C.sizeof(MX.SliceHeader), 32]
-    assert got == want, (got, want)
+def test_prototype_table_is_the_headers():
+    """abi.PROTOTYPES (what open_library() declares to ctypes) against include/*.h: exactly the declared functions, each with the declared
+    return type, parameter count and parameter classes."""
+    from x264_vs2008_amd.abi import PROTOTYPES
+    declared = {}
+    for header in HEADERS:
+        d = _declarations(header)
+        assert not set(d) & set(declared)
+        declared.update(d)
+    assert len(declared) > 100 and {v[0] for v in declared.values()} == set("ivpzsf")
+    assert sorted(PROTOTYPES) == sorted(declared), sorted(set(PROTOTYPES) ^ set(declared))
+    wrong = {n: (PROTOTYPES[n], declared[n]) for n in declared if PROTOTYPES[n] != declared[n]}
+    assert not wrong, "function: (table, header) %s" % wrong
+
+
+def test_records_match_header_layouts(tmp_path):
+    """Every ctypes record of abi.RECORDS against its C typedef: sizeof, and offsetof / size of every field by name, printed by one C program
+    generated from the records.  And the other way round: every typedef struct of the headers has a record or is listed in RAW_TYPEDEFS."""
+    from x264_vs2008_amd import tables                     # registers the seven records of x264hip_tables.h
+    from x264_vs2008_amd.abi import RECORDS
+    assert tables.PixelTable in RECORDS.values()
+    typedefs = [n for h in HEADERS + ("x264hip_tables.h",) for n in re.findall(STRUCT, _header(h), flags=re.S)]
+    assert len(typedefs) == len(set(typedefs)) > 30
+    assert not set(RECORDS) & set(RAW_TYPEDEFS)
+    assert sorted(typedefs) == sorted(set(RECORDS) | set(RAW_TYPEDEFS)), "typedef structs without a record / records without a typedef: %s" % sorted(set(typedefs) ^ (set(RECORDS) | set(RAW_TYPEDEFS)))
+    lines, want = [], {}
+    for cname in RAW_TYPEDEFS:
+        lines.append('printf("%s %%zu 0\\n", sizeof(%s));' % (cname, cname))
+        want[cname] = (RAW_TYPEDEFS[cname], 0)
+    for cname, rec in RECORDS.items():
+        lines.append('printf("%s %%zu 0\\n", sizeof(%s));' % (cname, cname))
+        want[cname] = (C.sizeof(rec), 0)
+        for field in rec._fields_:
+            f = field[0]
+            lines.append('printf("%s.%s %%zu %%zu\\n", sizeof(((%s *)0)->%s), offsetof(%s, %s));' % (cname, f, cname, f, cname, f))
+            want["%s.%s" % (cname, f)] = (getattr(rec, f).size, getattr(rec, f).offset)
+    prog = "#include <stdio.h>\n#include <stddef.h>\n" + "".join('#include "%s"\n' % h for h in HEADERS) + "int main(void) {\n" + "\n".join(lines) + "\nreturn 0; }\n"
+    src, exe = tmp_path / "layout.c", tmp_path / "layout.bin"
+    src.write_text(prog)
+    subprocess.run(["gcc", str(src), "-I", os.path.join(ROOT, "include"), "-o", str(exe)], check=True)
+    got = {}
+    for line in subprocess.check_output([str(exe)]).decode().splitlines():
+        key, size, offset = line.split()
+        got[key] = (int(size), int(offset))
+    assert len(got) == len(want) > 400
+    wrong = {k: (want[k], got[k]) for k in want if want[k] != got[k]}
+    assert not wrong, "record or field: ((size, offset) in ctypes, in C) %s" % wrong
+
+
+def test_every_call_site_passes_the_declared_argument_count():
+    """A wrong count raises only when the call runs, and most calls run only on a GPU: read them here.  Every call of a declared function in
+    the package, the tests, bench.py and __graft_entry__.py is positional, without star-arguments, and has the declared arity."""
+    from x264_vs2008_amd.abi import PROTOTYPES
+    files = glob.glob(os.path.join(ROOT, "x264_vs2008_amd", "*.py")) + glob.glob(os.path.join(ROOT, "tests", "*.py")) + \
+        [os.path.join(ROOT, "bench.py"), os.path.join(ROOT, "__graft_entry__.py")]
+    bad, n = [], 0
+    for path in files:
+        with open(path) as f:
+            tree = ast.parse(f.read(), path)
+        for call in (n for n in ast.walk(tree) if isinstance(n, ast.Call) and isinstance(n.func, ast.Attribute) and n.func.attr in PROTOTYPES):
+            n += 1
+            arity = len(PROTOTYPES[call.func.attr].split(":")[1])
+            if call.keywords or any(isinstance(a, ast.Starred) for a in call.args) or len(call.args) != arity:
+                bad.append("%s:%d %s takes %d positional arguments" % (os.path.relpath(path, ROOT), call.lineno, call.func.attr, arity))
+    assert n > 200, n
+    assert not bad, "\n  ".join(bad)
+
+
+def test_bare_integer_address_is_passed_at_full_width():
+    """What the prototypes are for: without them ctypes passes a Python integer as a 32-bit C int, and an address above 2^32 arrives cut in
+    half.  x264hip_cost_mv_table is host C that writes through its third argument."""
+    from x264_vs2008_amd import lib as L
+    from x264_vs2008_amd.slice import COST_SPAN
+    lib = L.open_library()
+    n = 2 * COST_SPAN + 1
+    big, want = np.zeros(1 << 22, np.int16), np.zeros(n, np.int16)           # (an allocation this large is mapped, far above 2^32)
+    assert big.ctypes.data >> 32, "the buffer's address fits 32 bits: the test would not see a truncation"
+    lib.x264hip_cost_mv_table(4, COST_SPAN, want.ctypes.data_as(C.c_void_p))
+    lib.x264hip_cost_mv_table(4, COST_SPAN, big.ctypes.data)
+    assert want.any() and np.array_equal(big[:n], want) and not big[n:].any()
+    with pytest.raises(C.ArgumentError):
+        lib.x264hip_cost_mv_table(4.0, COST_SPAN, want.ctypes.data_as(C.c_void_p))
 
 
 def test_init_fails_loudly_without_gpu_or_inits_with_one():
@@ -88,32 +157,6 @@ def test_init_fails_loudly_without_gpu_or_inits_with_one():
         assert not any(bool(f) for f in t.sad)
     else:
         assert rc == 0
-
-
-def test_table_struct_sizes_match_header():
-    """ctypes mirrors vs the C header: compile a tiny program printing sizeof() of each table."""
-    from x264_vs2008_amd import tables as T
-    prog = r'''
-#include <stdio.h>
-#include "x264hip.h"
-int main(void){ printf("%zu %zu %zu %zu %zu %zu %zu %zu %zu\n", sizeof(x264hip_pixel_function_t), sizeof(x264hip_dct_function_t),
- sizeof(x264hip_zigzag_function_t), sizeof(x264hip_quant_function_t), sizeof(x264hip_mc_functions_t),
- sizeof(x264hip_deblock_function_t), sizeof(x264hip_run_level_t), sizeof(x264hip_picture), sizeof(x264hip_me_params));
- printf("%zu %zu %zu %zu %zu %zu\n", sizeof(x264hip_mb_state), sizeof(x264hip_slice_params), sizeof(x264hip_slice_rd), sizeof(x264hip_slice_b),
- sizeof(x264hip_nr_state), sizeof(x264hip_deblock_params)); return 0; }
-'''
-    exe = os.path.join(ROOT, "tests", "_sizes.bin")
-    subprocess.run(["gcc", "-x", "c", "-", "-I", os.path.join(ROOT, "include"), "-o", exe], input=prog.encode(), check=True)
-    try:
-        got = [int(v) for v in subprocess.check_output([exe]).split()]
-    finally:
-        os.remove(exe)
-    from x264_vs2008_amd.frame import DeblockParams, MeParams, Picture
-    from x264_vs2008_amd.slice import MbState, NrState, SliceB, SliceParams, SliceRd
-    want = [C.sizeof(T.PixelTable), C.sizeof(T.DctTable), C.sizeof(T.ZigzagTable), C.sizeof(T.QuantTable), C.sizeof(T.McTable),
-            C.sizeof(T.DeblockTable), C.sizeof(T.RunLevel), C.sizeof(Picture), C.sizeof(MeParams),
-            C.sizeof(MbState), C.sizeof(SliceParams), C.sizeof(SliceRd), C.sizeof(SliceB), C.sizeof(NrState), C.sizeof(DeblockParams)]
-    assert got == want, (got, want)
 
 
 def test_cost_mv_table_properties():
@@ -175,7 +218,7 @@ def test_cost_mv_table_built_in_c_matches_twin_and_numpy(oracle_lib):
     oracle_lib.x264o_cost_mv_row.restype = C.c_void_p
     for qp in range(52):
         got = np.zeros(2 * COST_SPAN + 1, np.int16)
-        lib.x264hip_cost_mv_table(C.c_int(LAMBDA_TAB[qp]), C.c_int(COST_SPAN), got.ctypes.data_as(C.c_void_p))
+        lib.x264hip_cost_mv_table(LAMBDA_TAB[qp], COST_SPAN, got.ctypes.data_as(C.c_void_p))
         twin = np.ctypeslib.as_array((C.c_int16 * (2 * COST_SPAN + 1)).from_address(oracle_lib.x264o_cost_mv_row(qp)))
         assert np.array_equal(got, twin), qp
         assert np.array_equal(got.view(np.uint16), cost_mv_table(LAMBDA_TAB[qp], COST_SPAN)), qp
@@ -190,7 +233,6 @@ def test_nal_encode_matches_reference():
     from x264_vs2008_amd import lib as L
 
     lib = L.open_library()
-    lib.x264hip_nal_encode.restype = C.c_int
     ref_so = os.path.join(ROOT, "oracle", "_ref", "libx264ref.so")
     ref = None
     if os.path.exists(ref_so):

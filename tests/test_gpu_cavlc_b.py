@@ -66,7 +66,7 @@ def test_chain_table_writer_i_p_b_in_one_launch(hip_lib):
     cap = enc.payload_cap
     bufs = [dict(payload=DeviceArray(lib, (B, cap), np.uint8), payload_len=DeviceArray(lib, (B,), np.int32), mb_bits=DeviceArray(lib, (B, n_mb), np.int32)) for _ in range(3)]
     tb = lib.x264hip_chain_cavlc_bytes()
-    tab_host, tab_dev = lib.x264hip_host_alloc(C.c_size_t(tb * B)), DeviceArray(lib, (tb * B,), np.uint8)
+    tab_host, tab_dev = lib.x264hip_host_alloc(tb * B), DeviceArray(lib, (tb * B,), np.uint8)
     try:
         frames = []                                    # per coded frame: (slice type, qp, state, list-0 size)
         order = sl.coding_order(n, 0, 2)
@@ -87,7 +87,7 @@ def test_chain_table_writer_i_p_b_in_one_launch(hip_lib):
 
         ps = [params(k, bufs[0]) for k in range(3)]
         entries = (sl.ChainCavlc * 3)(*[sl.ChainCavlc(k, C.addressof(frames[k][2].st), C.addressof(ps[k])) for k in range(3)])
-        enc.ctx.check(lib.x264hip_cavlc_write_chains(enc.ctx.h, entries, 3, C.c_void_p(tab_host), tab_dev.p), "cavlc_write_chains")
+        enc.ctx.check(lib.x264hip_cavlc_write_chains(enc.ctx.h, entries, 3, tab_host, tab_dev.p), "cavlc_write_chains")
         single = [params(k, bufs[1 + k]) for k in range(2)]                 # the I and the P state, every chain, by the lock-step entry point
         for k in range(2):
             enc.ctx.check(lib.x264hip_cavlc_write_frame(enc.ctx.h, C.byref(frames[k][2].st), C.byref(single[k])), "cavlc_write_frame")
@@ -105,7 +105,7 @@ def test_chain_table_writer_i_p_b_in_one_launch(hip_lib):
     finally:
         enc.ctx.sync()
         tab_dev.free()
-        lib.x264hip_host_free(C.c_void_p(tab_host))
+        lib.x264hip_host_free(tab_host)
         for rb in bufs:
             for d in rb.values():
                 d.free()
@@ -162,7 +162,7 @@ def test_chain_table_mixing_cabac_and_cavlc_is_refused(hip_lib):
     e_cavlc = sl.ChainEncoder(hip_lib, w, h, cq, batch=2, cabac=0, **common)
     lib, c = hip_lib, e_cabac.ctx
     tb = lib.x264hip_chain_sweep_bytes()
-    tab_host, tab_dev = lib.x264hip_host_alloc(C.c_size_t(tb * 2)), DeviceArray(lib, (tb * 2,), np.uint8)
+    tab_host, tab_dev = lib.x264hip_host_alloc(tb * 2), DeviceArray(lib, (tb * 2,), np.uint8)
     try:
         y, u, v = rs.clip(w, h, 1)
         for b in range(2):
@@ -181,7 +181,7 @@ def test_chain_table_mixing_cabac_and_cavlc_is_refused(hip_lib):
                 entries[b] = ChainSweep(chain=b, fenc=C.addressof(e_cabac.fenc), refs=None, n_refs=0, recon=C.addressof(recon), params=C.addressof(p), l0=None,
                                         out=C.addressof(state.st))
             c.check(lib.x264hip_mb_state_clear_progress(c.h, C.byref(state.st)), "mb_state_clear_progress")
-            c.check(lib.x264hip_slice_sweep_chains(c.h, entries, 2, C.c_void_p(tab_host), tab_dev.p), "slice_sweep_chains")
+            c.check(lib.x264hip_slice_sweep_chains(c.h, entries, 2, tab_host, tab_dev.p), "slice_sweep_chains")
             c.sync()
 
         with pytest.raises(RuntimeError, match="all-CAVLC or not at all"):
@@ -191,6 +191,6 @@ def test_chain_table_mixing_cabac_and_cavlc_is_refused(hip_lib):
     finally:
         c.sync()
         tab_dev.free()
-        lib.x264hip_host_free(C.c_void_p(tab_host))
+        lib.x264hip_host_free(tab_host)
         e_cavlc.close()
         e_cabac.close()

@@ -79,7 +79,7 @@ def test_context_after_one_whose_b_stream_died_equals_reference(hip_lib, oracle_
     assert lib.x264hip_last_error() == b""
     enc = sl.ChainEncoder(lib, w, h, cqm, batch=2, write=1, **kw, **ekw)
     tb = lib.x264hip_chain_sweep_bytes()
-    tab_host = lib.x264hip_host_alloc(C.c_size_t(tb * 2))
+    tab_host = lib.x264hip_host_alloc(tb * 2)
     tab_dev = DeviceArray(lib, (tb * 2,), np.uint8)
     stream = ctx = None
     try:
@@ -116,7 +116,7 @@ def test_context_after_one_whose_b_stream_died_equals_reference(hip_lib, oracle_
 
         def launch(c):
             c.check(lib.x264hip_mb_state_clear_progress(c.h, C.byref(state.st)), "mb_state_clear_progress")
-            c.check(lib.x264hip_slice_sweep_chains(c.h, entries, 2, C.c_void_p(tab_host), tab_dev.p), "slice_sweep_chains")
+            c.check(lib.x264hip_slice_sweep_chains(c.h, entries, 2, tab_host, tab_dev.p), "slice_sweep_chains")
             c.sync()
             assert lib.x264hip_slice_sweep_status(c.h, C.byref(state.st)) == 0, lib.x264hip_last_error()
             got = {k: state.get(k) for k in ("mb_type", "mv", "ref", "cbp", "qp")}
@@ -126,11 +126,11 @@ def test_context_after_one_whose_b_stream_died_equals_reference(hip_lib, oracle_
         stream = lib.x264hip_stream_create()
         assert stream
         ctx = FrameCtx(lib, w, h, batch=2)                   # context A
-        ctx.check(lib.x264hip_frame_ctx_set_b_stream(ctx.h, C.c_void_p(stream)), "frame_ctx_set_b_stream")
+        ctx.check(lib.x264hip_frame_ctx_set_b_stream(ctx.h, stream), "frame_ctx_set_b_stream")
         got_a = launch(ctx)
         ctx.close()                                          # x264hip_frame_ctx_delete
         ctx = None
-        lib.x264hip_stream_destroy(C.c_void_p(stream))
+        lib.x264hip_stream_destroy(stream)
         stream = None
         ctx = FrameCtx(lib, w, h, batch=2)                   # context B: the library's own B stream, made by this launch
         got_b = launch(ctx)
@@ -141,9 +141,9 @@ def test_context_after_one_whose_b_stream_died_equals_reference(hip_lib, oracle_
         if ctx is not None:
             ctx.close()
         if stream:
-            lib.x264hip_stream_destroy(C.c_void_p(stream))
+            lib.x264hip_stream_destroy(stream)
         tab_dev.free()
-        lib.x264hip_host_free(C.c_void_p(tab_host))
+        lib.x264hip_host_free(tab_host)
         enc.close()
     for what, got in (("context A", got_a), ("context B", got_b)):
         for b, f in enumerate((3, 2)):                       # chain 0: the reference's coded frame 3 (P3); chain 1: its coded frame 2 (B1)

@@ -52,8 +52,6 @@ def test_frame_ctx_refuses_a_batch_beyond_its_limit(hip_lib):
     shared with whatever else runs on it, so "nothing allocated" is asked of 1024 refusals at once: had each kept even the ~98 KB statistics
     block a 4097-chain context starts with, they would hold ~100 MB, three times the slack left for other processes."""
     free0, free1, total = C.c_size_t(), C.c_size_t(), C.c_size_t()
-    hip_lib.x264hip_frame_ctx_new.restype = C.c_void_p
-    hip_lib.x264hip_last_error.restype = C.c_char_p
     d = Dims(width=1920, height=1080, batch=BATCH_LIMIT + 1)
     assert hip_lib.x264hip_mem_info(C.byref(free0), C.byref(total)) == 0
     for _ in range(1024):
@@ -64,7 +62,7 @@ def test_frame_ctx_refuses_a_batch_beyond_its_limit(hip_lib):
     d = Dims(width=1920, height=1080, batch=BATCH_LIMIT)
     h = hip_lib.x264hip_frame_ctx_new(C.byref(d), None)
     assert h, hip_lib.x264hip_last_error().decode()
-    hip_lib.x264hip_frame_ctx_delete(C.c_void_p(h))
+    hip_lib.x264hip_frame_ctx_delete(h)
 
 
 @pytest.mark.parametrize("B", [2048, BATCH_LIMIT])

@@ -19,6 +19,7 @@ from x264_vs2008_amd import slice as sl
 from paths import REF_SO
 from slice_util import run_chain2
 from x264_vs2008_amd.frame import DeviceArray
+from x264_vs2008_amd.stream import ChainSweep
 
 pytestmark = pytest.mark.gpu
 STATE = [k for k in LC.WHOLE if k not in ("mvr", "frame_info", "stat", "payload_len", "mb_bits")]
@@ -114,12 +115,6 @@ def test_three_chains_with_different_content_in_one_launch(hip_lib, cqm):
         enc.close()
 
 
-class ChainSweep(C.Structure):
-    """x264hip_chain_sweep"""
-    _fields_ = [("chain", C.c_int), ("fenc", C.c_void_p), ("refs", C.c_void_p), ("n_refs", C.c_int), ("recon", C.c_void_p),
-                ("params", C.c_void_p), ("l0", C.c_void_p), ("out", C.c_void_p)]
-
-
 def table_launch(hip_lib, cqm, size, frames, y, u, v, kw, qps):
     """Every frame of a batch of len(qps) chains (all fed the same clip) through x264hip_slice_sweep_chains, chain b at QP qps[b]: one
     ChainEncoder per QP value owns the tables of its chains, all of them share the first one's context, pictures and states.
@@ -131,7 +126,7 @@ def table_launch(hip_lib, cqm, size, frames, y, u, v, kw, qps):
     e0 = encs[qps[0]]
     lib, c = hip_lib, e0.ctx
     tb = lib.x264hip_chain_sweep_bytes()
-    tab_host = lib.x264hip_host_alloc(C.c_size_t(tb * B))
+    tab_host = lib.x264hip_host_alloc(tb * B)
     tab_dev = DeviceArray(lib, (tb * B,), np.uint8)
     out = []
     try:
@@ -160,7 +155,7 @@ def table_launch(hip_lib, cqm, size, frames, y, u, v, kw, qps):
                 entries[b] = ChainSweep(chain=b, fenc=C.addressof(e0.fenc), refs=C.cast(arr, C.c_void_p) if arr else None, n_refs=len(refs),
                                         recon=C.addressof(recon), params=C.addressof(p), l0=C.addressof(refs[0][1].st) if refs else None, out=C.addressof(state.st))
             c.check(lib.x264hip_mb_state_clear_progress(c.h, C.byref(state.st)), "mb_state_clear_progress")
-            c.check(lib.x264hip_slice_sweep_chains(c.h, entries, B, C.c_void_p(tab_host), tab_dev.p), "slice_sweep_chains")
+            c.check(lib.x264hip_slice_sweep_chains(c.h, entries, B, tab_host, tab_dev.p), "slice_sweep_chains")
             e0.last, e0.last_ctx, e0.last_bufs, e0.last_is_b, e0.last_poc = (recon, state), c, e0.rd_bufs, False, 2 * f
             e0.status()
             rec = [np.stack([c.download(recon, nm, padded=False, b=b) for b in range(B)]) for nm in ("y", "u", "v")]
@@ -170,7 +165,7 @@ def table_launch(hip_lib, cqm, size, frames, y, u, v, kw, qps):
     finally:
         c.sync()
         tab_dev.free()
-        lib.x264hip_host_free(C.c_void_p(tab_host))
+        lib.x264hip_host_free(tab_host)
         for e in encs.values():
             e.close()
     return out

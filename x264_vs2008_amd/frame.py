@@ -1,4 +1,4 @@
-"""Host-side mirror of the frame level of include/x264hip.h (ctypes).
+"""Host side of the frame level of include/x264hip.h (ctypes; the records -- Dims, Picture, the parameter structs -- are abi.py's).
 
 Thin: it owns no arithmetic.  Device buffers other than pictures are
 DeviceArray objects backed by the library's own malloc/memcpy entry points
@@ -9,46 +9,9 @@ import ctypes as C
 
 import numpy as np
 
+from .abi import CqmTables, DeblockParams, Dims, Me16Params, MeParams, Picture, ResidualParams
+
 PADH = PADV = 32
-
-
-class Dims(C.Structure):
-    _fields_ = [("width", C.c_int), ("height", C.c_int), ("mb_w", C.c_int), ("mb_h", C.c_int),
-                ("stride_y", C.c_int), ("stride_c", C.c_int), ("lines_y", C.c_int), ("lines_c", C.c_int),
-                ("batch", C.c_int)]
-
-
-class Picture(C.Structure):
-    _fields_ = [("plane", C.c_void_p * 3), ("filtered", C.c_void_p * 4), ("lowres", C.c_void_p * 4),
-                ("integral", C.c_void_p), ("stride_lowres", C.c_int), ("width_lowres", C.c_int),
-                ("lines_lowres", C.c_int)]
-
-
-class MeParams(C.Structure):
-    _fields_ = [("range", C.c_int), ("cost_mv", C.c_void_p), ("cost_mv_range", C.c_int),
-                ("centers", C.c_void_p), ("mvp", C.c_void_p), ("sad_surface", C.c_void_p),
-                ("mv_range", C.c_int)]
-
-
-class Me16Params(C.Structure):
-    _fields_ = [("me_method", C.c_int), ("me_range", C.c_int), ("subme", C.c_int), ("chroma_me", C.c_int),
-                ("mv_range", C.c_int), ("cost_mv", C.c_void_p), ("cost_mv_range", C.c_int),
-                ("mvp", C.c_void_p), ("mvc", C.c_void_p), ("n_mvc", C.c_void_p), ("ref_cost", C.c_int * 8)]
-
-
-class ResidualParams(C.Structure):
-    _fields_ = [("qp", C.c_int), ("qp_chroma", C.c_int), ("transform8x8", C.c_int), ("b_interlaced", C.c_int),
-                ("quant4_mf", C.c_void_p), ("quant4_bias", C.c_void_p),
-                ("quant8_mf", C.c_void_p), ("quant8_bias", C.c_void_p),
-                ("dequant4_mf", C.c_void_p), ("dequant8_mf", C.c_void_p),
-                ("mv4x4_out", C.c_void_p), ("ref_out", C.c_void_p)]
-
-
-class DeblockParams(C.Structure):
-    _fields_ = [("mb_type", C.c_void_p), ("qp", C.c_void_p), ("nnz", C.c_void_p), ("transform8x8", C.c_void_p),
-                ("mv", C.c_void_p), ("ref", C.c_void_p),
-                ("alpha_c0_offset", C.c_int), ("beta_offset", C.c_int), ("chroma_qp_offset", C.c_int),
-                ("state_layout", C.c_int), ("sub8x8", C.c_int)]
 
 
 class DeviceArray:
@@ -57,7 +20,7 @@ class DeviceArray:
     def __init__(self, lib, shape, dtype, init=None):
         self.lib, self.shape, self.dtype = lib, tuple(np.atleast_1d(shape)), np.dtype(dtype)
         self.nbytes = int(np.prod(self.shape)) * self.dtype.itemsize
-        self.ptr = lib.x264hip_malloc(C.c_size_t(self.nbytes))
+        self.ptr = lib.x264hip_malloc(self.nbytes)
         if not self.ptr:
             raise MemoryError("x264hip_malloc(%d) failed" % self.nbytes)
         if init is not None:
@@ -70,11 +33,11 @@ class DeviceArray:
     def set(self, arr):
         arr = np.ascontiguousarray(arr, dtype=self.dtype)
         assert arr.nbytes == self.nbytes
-        assert self.lib.x264hip_memcpy_h2d(self.p, arr.ctypes.data_as(C.c_void_p), C.c_size_t(self.nbytes)) == 0
+        assert self.lib.x264hip_memcpy_h2d(self.p, arr.ctypes.data_as(C.c_void_p), self.nbytes) == 0
 
     def get(self):
         out = np.zeros(self.shape, self.dtype)
-        assert self.lib.x264hip_memcpy_d2h(out.ctypes.data_as(C.c_void_p), self.p, C.c_size_t(self.nbytes)) == 0
+        assert self.lib.x264hip_memcpy_d2h(out.ctypes.data_as(C.c_void_p), self.p, self.nbytes) == 0
         return out
 
     def free(self):
@@ -93,7 +56,7 @@ class FrameCtx:
         self.lib = lib
         self.batch = batch
         self.dims = Dims(width=width, height=height, batch=batch)
-        self.h = lib.x264hip_frame_ctx_new(C.byref(self.dims), C.c_void_p(stream))
+        self.h = lib.x264hip_frame_ctx_new(C.byref(self.dims), stream)
         if not self.h:
             raise RuntimeError("x264hip_frame_ctx_new failed: %s" % lib.x264hip_last_error().decode())
         self.h = C.c_void_p(self.h)
@@ -117,11 +80,11 @@ class FrameCtx:
         return pic
 
     def copy_element(self, dst, dst_b, src, src_b):
-        self.check(self.lib.x264hip_picture_copy_element(self.h, C.byref(dst), C.c_int(dst_b), C.byref(src), C.c_int(src_b)), "picture_copy_element")
+        self.check(self.lib.x264hip_picture_copy_element(self.h, C.byref(dst), dst_b, C.byref(src), src_b), "picture_copy_element")
 
     def synth(self, pic, t0, t_stride=0):
         """Element b of `pic` becomes frame t0 + b * t_stride of the synthetic clip (x264hip_picture_synth; synth.frame on the device)."""
-        self.check(self.lib.x264hip_picture_synth(self.h, C.byref(pic), C.c_int(t0), C.c_int(t_stride)), "picture_synth")
+        self.check(self.lib.x264hip_picture_synth(self.h, C.byref(pic), t0, t_stride), "picture_synth")
 
     def select(self, b):
         """Choose the batch element that upload / download / x264hip_ssd_frame address."""
@@ -202,14 +165,6 @@ class CqmDevice:
             v.free()
 
 
-class CqmTables(C.Structure):
-    """x264hip_cqm_tables (include/x264hip.h)."""
-    _fields_ = [("quant4_mf", C.c_uint16 * (4 * 52 * 16)), ("quant4_bias", C.c_uint16 * (4 * 52 * 16)),
-                ("quant8_mf", C.c_uint16 * (2 * 52 * 64)), ("quant8_bias", C.c_uint16 * (2 * 52 * 64)),
-                ("dequant4_mf", C.c_int32 * (4 * 6 * 16)), ("dequant8_mf", C.c_int32 * (2 * 6 * 64)),
-                ("unquant4_mf", C.c_int32 * (4 * 52 * 16)), ("unquant8_mf", C.c_int32 * (2 * 52 * 64))]
-
-
 CQM_SHAPES = {"quant4_mf": (4, 52, 16), "quant4_bias": (4, 52, 16), "quant8_mf": (2, 52, 64), "quant8_bias": (2, 52, 64),
               "dequant4_mf": (4, 6, 16), "dequant8_mf": (2, 6, 64), "unquant4_mf": (4, 52, 16), "unquant8_mf": (2, 52, 64)}
 
@@ -240,7 +195,7 @@ def cqm_init(lib, scaling_lists=None, luma_deadzone=None, qp_min=0):
             arr[i] = a.ctypes.data_as(C.POINTER(C.c_uint8))
         lists = arr
     dz = (C.c_int * 2)(*luma_deadzone) if luma_deadzone is not None else None
-    if lib.x264hip_cqm_init(lists, dz, C.c_int(qp_min), C.byref(t)) != 0:
+    if lib.x264hip_cqm_init(lists, dz, qp_min, C.byref(t)) != 0:
         raise RuntimeError("x264hip_cqm_init failed: %s" % lib.x264hip_last_error().decode())
     return {k: np.ctypeslib.as_array(getattr(t, k)).reshape(shape).copy() for k, shape in CQM_SHAPES.items()}
 

@@ -7,6 +7,8 @@ import ctypes as C
 import os
 import subprocess
 
+from .abi import CLASSES, PROTOTYPES, Cfg
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 SO_PATH = os.path.join(_HERE, "libx264hip.so")
 _lib = None
@@ -14,23 +16,6 @@ _lib = None
 
 class X264HipError(RuntimeError):
     pass
-
-
-class Cfg(C.Structure):
-    _fields_ = [("device", C.c_int), ("arena_bytes", C.c_size_t)]
-
-
-# The prototypes ctypes cannot guess (it assumes int everywhere): the return type of every exported function that does not return int, and the
-# argument types of every function that takes a float by value.  Declared here once, for every user of the library.
-RESTYPES = {
-    C.c_char_p: ("x264hip_last_error",),
-    C.c_float: ("x264hip_event_elapsed_ms",),
-    C.c_size_t: ("x264hip_lookahead_state_bytes", "x264hip_lookahead_task_bytes", "x264hip_chain_sweep_bytes", "x264hip_chain_cavlc_bytes"),
-    C.c_void_p: ("x264hip_malloc", "x264hip_host_alloc", "x264hip_stream_create", "x264hip_stream_create_high_priority",
-                 "x264hip_stream_create_cu_range", "x264hip_event_create", "x264hip_frame_ctx_new", "x264hip_frame_ctx_stream",
-                 "x264hip_lookahead_new"),
-}
-ARGTYPES = {"x264hip_adaptive_quant_frame": (C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p)}
 
 
 def build(verbose=False):
@@ -52,15 +37,15 @@ def build_examples():
 
 
 def open_library():
-    """dlopen only (no device needed), with the prototypes of RESTYPES / ARGTYPES declared."""
+    """dlopen only (no device needed), with the prototype of every exported function declared (abi.PROTOTYPES): ctypes then converts
+    each argument to the declared C type -- an address at its full width -- and refuses a wrong argument count or class."""
     if not os.path.exists(SO_PATH):
         raise X264HipError("libx264hip.so not built: run `python -c 'import __graft_entry__ as g; g.build()'`")
     lib = C.CDLL(SO_PATH)
-    for restype, names in RESTYPES.items():
-        for name in names:
-            getattr(lib, name).restype = restype
-    for name, argtypes in ARGTYPES.items():
-        getattr(lib, name).argtypes = argtypes
+    for name, proto in PROTOTYPES.items():
+        ret, args = proto.split(":")
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = CLASSES[ret], [CLASSES[a] for a in args]
     return lib
 
 

@@ -1,5 +1,5 @@
-"""Host mirror of the encoder's frame queue for one GOP chain: ctypes over x264hip_lookahead_* (include/x264hip.h; the logic is the
-library's host C, csrc/lookahead_host.hip -- x264_slicetype_decide, x264_rc_analyse_slice, the CQP / CRF rate control).
+"""Host mirror of the encoder's frame queue for one GOP chain: ctypes over x264hip_lookahead_* (include/x264hip.h, records in abi.py; the logic
+is the library's host C, csrc/lookahead_host.hip -- x264_slicetype_decide, x264_rc_analyse_slice, the CQP / CRF rate control).
 
     la = Lookahead(lib, LookaheadParams(...))
     la.put()                      # a picture enters frames.next (R/encoder/encoder.c:1404-1421)
@@ -14,18 +14,12 @@ library's host C, csrc/lookahead_host.hip -- x264_slicetype_decide, x264_rc_anal
 Nothing here computes a cost: the GPU does (x264hip_lookahead_cost_frames through x264_vs2008_amd.slice), or, in the CPU tests, the oracle."""
 import ctypes as C
 
+from .abi import Frame, LookaheadParams, LookParams, LookSlot, LookTask, Need
+
 NONE, FRAME, NEED, END = 0, 1, 2, 3
 TYPE_IDR, TYPE_I, TYPE_P, TYPE_B = 1, 2, 3, 5          # R/x264.h:116-121
 RC_CQP, RC_CRF = 0, 1
 MAX_NEED = 16
-
-
-class LookaheadParams(C.Structure):
-    """x264hip_lookahead_params"""
-    _fields_ = [("mb_w", C.c_int), ("mb_h", C.c_int), ("bframes", C.c_int), ("b_adapt", C.c_int), ("bframe_bias", C.c_int),
-                ("keyint_max", C.c_int), ("keyint_min", C.c_int), ("scenecut_threshold", C.c_int), ("pre_scenecut", C.c_int),
-                ("rc_method", C.c_int), ("qp_constant", C.c_int), ("rf_constant", C.c_float), ("ip_factor", C.c_float),
-                ("pb_factor", C.c_float), ("qcompress", C.c_float), ("qp_min", C.c_int), ("qp_max", C.c_int), ("qp_step", C.c_int)]
 
 
 def make_params(mb_w, mb_h, bframes=0, b_adapt=1, bframe_bias=0, keyint_max=250, keyint_min=0, scenecut_threshold=40, pre_scenecut=1,
@@ -41,20 +35,8 @@ def make_params(mb_w, mb_h, bframes=0, b_adapt=1, bframe_bias=0, keyint_max=250,
                            RC_CQP if crf is None else RC_CRF, qp, 0.0 if crf is None else crf, ip_factor, pb_factor, qcompress, qp_min, qp_max, qp_step)
 
 
-class Need(C.Structure):
-    """x264hip_look_need"""
-    _fields_ = [("b", C.c_int), ("p0", C.c_int), ("p1", C.c_int), ("do_search", C.c_int * 2), ("speculative", C.c_int)]
-
-
-class Frame(C.Structure):
-    """x264hip_look_frame"""
-    _fields_ = [("frame", C.c_int), ("type", C.c_int), ("poc", C.c_int), ("kept_as_ref", C.c_int), ("qp", C.c_int), ("f_qpm", C.c_float),
-                ("ref0_frame", C.c_int), ("ref1_frame", C.c_int), ("lowres_l0", C.c_int), ("lowres_l1", C.c_int), ("i_satd", C.c_int),
-                ("frame_num_reset", C.c_int)]
-
-
 def bind(lib):
-    """Nothing left to do: lib.open_library() declares the prototypes that matter.  Kept for its callers."""
+    """Nothing left to do: lib.open_library() declares every prototype.  Kept for its callers."""
     return lib
 
 
@@ -62,7 +44,7 @@ class Lookahead:
     def __init__(self, lib, params):
         self.lib = lib
         self.params = params
-        self.h = C.c_void_p(lib.x264hip_lookahead_new(C.byref(params)))      # as a pointer: a bare integer would be passed on as a C int
+        self.h = lib.x264hip_lookahead_new(C.byref(params))
         if not self.h:
             raise ValueError("x264hip_lookahead_new refused the parameters (bframes > 16, unknown rate control, ...)")
         self._need = (Need * MAX_NEED)()
@@ -123,23 +105,6 @@ class Lookahead:
 # ------------------------------------------------------------------------------------------------------------------------------------
 # The device half: every chain's lookahead data in HBM and the batched cost kernel (x264hip_lookahead_cost_frames).
 
-class LookSlot(C.Structure):
-    """x264hip_look_slot"""
-    _fields_ = [("pic", C.c_void_p), ("intra_cost", C.c_void_p), ("mv", C.c_void_p), ("mv_cost", C.c_void_p)]
-
-
-class LookTask(C.Structure):
-    """x264hip_look_task"""
-    _fields_ = [("chain", C.c_int), ("slot_b", C.c_int), ("slot_p0", C.c_int), ("slot_p1", C.c_int), ("d0", C.c_int), ("d1", C.c_int),
-                ("do_search", C.c_int * 2)]
-
-
-class LookParams(C.Structure):
-    """x264hip_look_params"""
-    _fields_ = [("me_method", C.c_int), ("me_range", C.c_int), ("weighted_bipred", C.c_int), ("bframes", C.c_int), ("bframe_bias", C.c_int),
-                ("subme_param", C.c_int), ("lossless", C.c_int), ("cost_mv", C.c_void_p), ("cost_mv_range", C.c_int)]
-
-
 COST_SPAN = 2 * 4 * 2048      # p_cost_mv reaches +-2*4*2048 quarter-pels (R/encoder/analyse.c:191-198)
 
 
@@ -172,15 +137,15 @@ class LookaheadDevice:
         for i in range(n_slots):
             self.slots[i] = LookSlot(C.addressof(self.pics[i]), self.intra[i].ptr, self.mv[i].ptr, self.mv_cost[i].ptr)
         tab = np.zeros(2 * COST_SPAN + 1, np.int16)
-        lib.x264hip_cost_mv_table(C.c_int(1), C.c_int(COST_SPAN), tab.ctypes.data_as(C.c_void_p))      # a->i_lambda = x264_lambda_tab[12] = 1
+        lib.x264hip_cost_mv_table(1, COST_SPAN, tab.ctypes.data_as(C.c_void_p))      # a->i_lambda = x264_lambda_tab[12] = 1
         self.cost_mv = DeviceArray(lib, tab.shape, np.int16, tab)
         self.params = LookParams(me_method, me_range, weightb, bframes, bframe_bias, subme, lossless, self.cost_mv.ptr, COST_SPAN)
         self.max_tasks = max_tasks or 8 * ctx.batch
         tb = lib.x264hip_lookahead_task_bytes()
-        self.staging = lib.x264hip_host_alloc(C.c_size_t(tb * self.max_tasks))
+        self.staging = lib.x264hip_host_alloc(tb * self.max_tasks)
         self.tasks_dev = DeviceArray(lib, (tb * self.max_tasks,), np.uint8)
         self.out_dev = DeviceArray(lib, (self.max_tasks, 4), np.int32)
-        self.out_host = lib.x264hip_host_alloc(C.c_size_t(16 * self.max_tasks))
+        self.out_host = lib.x264hip_host_alloc(16 * self.max_tasks)
         if not self.staging or not self.out_host:
             raise MemoryError("x264hip_host_alloc")
         self.n_launches = self.n_tasks_run = 0
@@ -218,9 +183,9 @@ class LookaheadDevice:
                 for f in (b, p0, p1):
                     assert self.frame_of_slot[self.slot(f)] == f, "input frame %d is no longer in its lookahead slot" % f
                 arr[i] = LookTask(chain, self.slot(b), self.slot(p0), self.slot(p1), b - p0, p1 - b, (C.c_int * 2)(ds0, ds1))
-            ctx.check(lib.x264hip_lookahead_cost_frames(ctx.h, self.slots, self.n_slots, arr, len(part), C.byref(self.params), C.c_void_p(self.staging),
+            ctx.check(lib.x264hip_lookahead_cost_frames(ctx.h, self.slots, self.n_slots, arr, len(part), C.byref(self.params), self.staging,
                                                         self.tasks_dev.p, self.out_dev.p), "lookahead_cost_frames")
-            ctx.check(lib.x264hip_memcpy_d2h_async(C.c_void_p(self.out_host), self.out_dev.p, C.c_size_t(16 * len(part)), C.c_void_p(ctx.stream)), "memcpy_d2h_async")
+            ctx.check(lib.x264hip_memcpy_d2h_async(self.out_host, self.out_dev.p, 16 * len(part), ctx.stream), "memcpy_d2h_async")
             ctx.sync()
             res = np.ctypeslib.as_array(C.cast(self.out_host, C.POINTER(C.c_int32)), (len(part), 4))
             out[base:base + len(part)] = res[:, :3]
@@ -236,7 +201,7 @@ class LookaheadDevice:
         assert 0 < len(tasks) <= self.max_tasks
         if not hasattr(self, "_ring"):
             tb = lib.x264hip_lookahead_task_bytes()
-            self._ring = [dict(staging=lib.x264hip_host_alloc(C.c_size_t(tb * self.max_tasks)), out=lib.x264hip_host_alloc(C.c_size_t(16 * self.max_tasks)),
+            self._ring = [dict(staging=lib.x264hip_host_alloc(tb * self.max_tasks), out=lib.x264hip_host_alloc(16 * self.max_tasks),
                                ev=lib.x264hip_event_create(), busy=False) for _ in range(16)]
         slot = next((r for r in self._ring if not r["busy"]), None)
         if slot is None:
@@ -246,9 +211,9 @@ class LookaheadDevice:
             for f in (b, p0, p1):
                 assert self.frame_of_slot[self.slot(f)] == f, "input frame %d is no longer in its lookahead slot" % f
             arr[i] = LookTask(chain, self.slot(b), self.slot(p0), self.slot(p1), b - p0, p1 - b, (C.c_int * 2)(ds0, ds1))
-        ctx.check(lib.x264hip_lookahead_cost_frames(ctx.h, self.slots, self.n_slots, arr, len(tasks), C.byref(self.params), C.c_void_p(slot["staging"]),
-                                                    C.c_void_p(slot["staging"]), C.c_void_p(slot["out"])), "lookahead_cost_frames")
-        lib.x264hip_event_record(C.c_void_p(slot["ev"]), C.c_void_p(ctx.stream))
+        ctx.check(lib.x264hip_lookahead_cost_frames(ctx.h, self.slots, self.n_slots, arr, len(tasks), C.byref(self.params), slot["staging"],
+                                                    slot["staging"], slot["out"]), "lookahead_cost_frames")
+        lib.x264hip_event_record(slot["ev"], ctx.stream)
         slot["busy"], slot["n"] = True, len(tasks)
         self.n_launches += 1
         self.n_tasks_run += len(tasks)
@@ -256,7 +221,7 @@ class LookaheadDevice:
 
     def poll(self, handle):
         """None while the launch is running, then its results (int32 [n][3])."""
-        if self.lib.x264hip_event_query(C.c_void_p(handle["ev"])) != 1:
+        if self.lib.x264hip_event_query(handle["ev"]) != 1:
             return None
         res = self.np.ctypeslib.as_array(C.cast(handle["out"], C.POINTER(C.c_int32)), (handle["n"], 4))[:, :3].copy()
         handle["busy"] = False
@@ -275,12 +240,12 @@ class LookaheadDevice:
         for a in self.intra + self.mv + self.mv_cost + [self.cost_mv, self.tasks_dev, self.out_dev]:
             a.free()
         for r in getattr(self, "_ring", []):
-            self.lib.x264hip_host_free(C.c_void_p(r["staging"])); self.lib.x264hip_host_free(C.c_void_p(r["out"]))
-            self.lib.x264hip_event_destroy(C.c_void_p(r["ev"]))
+            self.lib.x264hip_host_free(r["staging"]); self.lib.x264hip_host_free(r["out"])
+            self.lib.x264hip_event_destroy(r["ev"])
         self._ring = []
         for p in (self.staging, self.out_host):
             if p:
-                self.lib.x264hip_host_free(C.c_void_p(p))
+                self.lib.x264hip_host_free(p)
         self.staging = self.out_host = None
 
 

@@ -1,6 +1,7 @@
 """The Annex B stream around the sweep's payloads: what x264_encoder_encode writes per call (R/encoder/encoder.c:1548-1600) -- the version
 SEI with frame 0, SPS + PPS with every IDR, then the slice NAL -- built from the library's host C (include/x264hip_stream.h:
-x264hip_validate_parameters, x264hip_sps_write / _pps_write / _sei_version_write, x264hip_slice_nal, x264hip_nal_encode).
+x264hip_validate_parameters, x264hip_sps_write / _pps_write / _sei_version_write, x264hip_slice_nal, x264hip_nal_encode; EncoderParams and
+SliceHeader, the records of that header, are abi.py's).
 
     p = mux.encoder_params(lib, width=352, height=288, rc_method=mux.RC_CQP, qp_constant=26, cabac=0, ...)      # validated like x264_encoder_open
     m = mux.AnnexB(lib, p)
@@ -11,36 +12,12 @@ the frame_num of the pictures kept as references.  The reference of this version
 so neither does this; beyond 2^log2_max_frame_num reference pictures the reference's own header is corrupt and this one is not the same."""
 import ctypes as C
 
+from .abi import EncoderParams, SliceHeader
+
 RC_CQP, RC_CRF = 0, 1
 TYPE_IDR, TYPE_I, TYPE_P, TYPE_BREF, TYPE_B = 1, 2, 3, 4, 5            # X264_TYPE_*, R/x264.h:131-136
 NAL_SLICE, NAL_SLICE_IDR, NAL_SEI, NAL_SPS, NAL_PPS = 1, 5, 6, 7, 8
 PRIORITY_DISPOSABLE, PRIORITY_HIGH, PRIORITY_HIGHEST = 0, 2, 3
-
-
-class EncoderParams(C.Structure):
-    """x264hip_encoder_params (include/x264hip_stream.h)"""
-    _fields_ = [("width", C.c_int), ("height", C.c_int), ("fps_num", C.c_int), ("fps_den", C.c_int), ("level_idc", C.c_int), ("threads", C.c_int),
-                ("frame_reference", C.c_int), ("keyint_max", C.c_int), ("keyint_min", C.c_int), ("scenecut_threshold", C.c_int), ("pre_scenecut", C.c_int),
-                ("bframe", C.c_int), ("bframe_adaptive", C.c_int), ("bframe_bias", C.c_int), ("bframe_pyramid", C.c_int),
-                ("deblocking_filter", C.c_int), ("deblocking_filter_alphac0", C.c_int), ("deblocking_filter_beta", C.c_int),
-                ("cabac", C.c_int), ("cabac_init_idc", C.c_int), ("interlaced", C.c_int), ("cqm_preset", C.c_int),
-                ("intra", C.c_uint), ("inter", C.c_uint),
-                ("transform_8x8", C.c_int), ("weighted_bipred", C.c_int), ("direct_mv_pred", C.c_int), ("chroma_qp_offset", C.c_int),
-                ("me_method", C.c_int), ("me_range", C.c_int), ("mv_range", C.c_int), ("subpel_refine", C.c_int), ("chroma_me", C.c_int),
-                ("mixed_references", C.c_int), ("trellis", C.c_int), ("fast_pskip", C.c_int), ("dct_decimate", C.c_int), ("noise_reduction", C.c_int),
-                ("psy_rd", C.c_float), ("psy_trellis", C.c_float), ("luma_deadzone", C.c_int * 2),
-                ("rc_method", C.c_int), ("qp_constant", C.c_int), ("qp_min", C.c_int), ("qp_max", C.c_int), ("qp_step", C.c_int),
-                ("rf_constant", C.c_float), ("ip_factor", C.c_float), ("pb_factor", C.c_float), ("qcompress", C.c_float),
-                ("aq_mode", C.c_int), ("aq_strength", C.c_float), ("scaling_list", C.c_void_p * 6),
-                ("d_valid", C.c_int), ("d_lossless", C.c_int), ("d_profile_idc", C.c_int), ("d_num_ref_frames", C.c_int), ("d_num_reorder_frames", C.c_int),
-                ("d_log2_max_frame_num", C.c_int), ("d_log2_max_poc_lsb", C.c_int), ("d_mb_width", C.c_int), ("d_mb_height", C.c_int),
-                ("d_pic_init_qp", C.c_int), ("d_log2_max_mv_length", C.c_int), ("d_psy_rd_fix8", C.c_int)]
-
-
-class SliceHeader(C.Structure):
-    """x264hip_slice_header"""
-    _fields_ = [("nal_type", C.c_int), ("nal_ref_idc", C.c_int), ("slice_type", C.c_int), ("frame_num", C.c_int), ("idr_pic_id", C.c_int),
-                ("poc", C.c_int), ("qp", C.c_int), ("n_ref0", C.c_int), ("n_ref1", C.c_int), ("direct_spatial", C.c_int), ("ref_frame_num", C.c_int * 16)]
 
 
 def _err(lib):

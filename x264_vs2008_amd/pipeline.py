@@ -78,11 +78,11 @@ class PFramePass:
         for i, ref in enumerate(refs):
             if self.me_events is not None:
                 e0, e1 = L.x264hip_event_create(), L.x264hip_event_create()
-                L.x264hip_event_record(C.c_void_p(e0), C.c_void_p(c.stream))
+                L.x264hip_event_record(e0, c.stream)
             c.check(L.x264hip_me_fullpel_frame(h, C.byref(cur), C.byref(ref), C.byref(self.me_p), self.mv9[i].p, self.cost9[i].p),
                     "me_fullpel_frame")
             if self.me_events is not None:
-                L.x264hip_event_record(C.c_void_p(e1), C.c_void_p(c.stream))
+                L.x264hip_event_record(e1, c.stream)
                 self.me_events.append((e0, e1))
             c.check(L.x264hip_me_subpel_frame(h, C.byref(cur), C.byref(ref), C.byref(self.me_p), self.mv9[i].p, self.mvq[i].p,
                                               self.costq[i].p), "me_subpel_frame")

@@ -1,5 +1,5 @@
-"""Host-side mirror of the macroblock sweep (include/x264hip.h: x264hip_slice_sweep_frame) and a
-chain encoder around it: I frame, then P frames, every frame kept as reference -- the sequencing
+"""Host side of the macroblock sweep (include/x264hip.h: x264hip_slice_sweep_frame; its records -- MbState, SliceParams, SliceRd,
+SliceB ... -- are abi.py's) and a chain encoder around it: I frame, then P frames, every frame kept as reference -- the sequencing
 x264_encoder_encode / x264_slice_write / x264_fdec_filter_row do on the host
 (R/encoder/encoder.c:1316-1560, 1141-1291, 983-1056), restricted to CQP without B-frames.
 
@@ -10,72 +10,17 @@ import math
 
 import numpy as np
 
-from .frame import LAMBDA_TAB, CqmDevice, DeblockParams, DeviceArray, FrameCtx
+from .abi import STATE_FIELDS, CavlcParams, ChainCavlc, DeblockParams, MbState, NrState, SliceB, SliceParams, SliceRd
+from .frame import LAMBDA_TAB, CqmDevice, DeviceArray, FrameCtx
 
 SLICE_P, SLICE_B, SLICE_I = 0, 1, 2
 I_4x4, I_8x8, I_16x16, I_PCM, P_L0, P_8x8, P_SKIP = range(7)
 COST_SPAN = 2 * 4 * 2048      # p_cost_mv reaches +-2*4*2048 quarter-pels (R/encoder/analyse.c:191-198)
 
-STATE_FIELDS = [("mb_type", np.int8, ()), ("partition", np.int8, ()), ("sub_partition", np.int8, (4,)), ("ref", np.int8, (4,)), ("i4mode", np.int8, (16,)),
-                ("i16mode", np.int8, ()), ("chroma_mode", np.int8, ()), ("qp", np.int8, ()), ("t8", np.int8, ()),
-                ("mv", np.int16, (16, 2)), ("mvr", np.int16, None), ("cbp", np.int16, ()), ("nnz", np.uint8, (27,)),
-                ("luma", np.int16, (256,)), ("luma_dc", np.int16, (16,)), ("chroma_dc", np.int16, (8,)), ("chroma_ac", np.int16, (128,)),
-                ("cost_intra", np.int32, ()), ("cost_inter", np.int32, ()), ("cost_intra_alt", np.int32, ())]
-
-
-class MbState(C.Structure):
-    _fields_ = [(name, C.c_void_p) for name, _, _ in STATE_FIELDS] + \
-               [("progress", C.c_void_p), ("poc", C.c_int), ("n_ref0", C.c_int), ("inv_ref_poc", C.c_int * 8), ("mvd", C.c_void_p),
-                ("mv1", C.c_void_p), ("ref1", C.c_void_p), ("mvr1", C.c_void_p), ("mvd1", C.c_void_p), ("skipbp", C.c_void_p),
-                ("ref_poc", C.c_int * 8)]
-
-
-class SliceB(C.Structure):
-    """x264hip_slice_b: list 1 of a B slice and what direct prediction reads."""
-    _fields_ = [("fref1", C.c_void_p), ("l1_state", C.c_void_p), ("ref1_poc", C.c_int), ("weightb", C.c_int), ("lowres_mv1", C.c_void_p),
-                ("direct_spatial", C.c_int), ("direct_score", C.c_void_p)]
-
-
-class SliceRd(C.Structure):
-    """x264hip_slice_rd: the raster-order variant of the sweep (RD levels, trellis, adaptive quantisation, the entropy coder in the loop)."""
-    _fields_ = [("trellis", C.c_int), ("psy_rd", C.c_int), ("write", C.c_int), ("cabac_init_idc", C.c_int), ("i_frame", C.c_int),
-                ("qp_min", C.c_int), ("qp_max", C.c_int), ("f_qpm", C.c_float), ("aq_offset", C.c_void_p), ("cost_mv_all", C.c_void_p),
-                ("unquant4_mf", C.c_void_p), ("unquant8_mf", C.c_void_p), ("payload", C.c_void_p), ("payload_cap", C.c_int),
-                ("payload_len", C.c_void_p), ("mb_bits", C.c_void_p), ("stale", C.c_void_p), ("i_frame_stride", C.c_int)]
-
-
-class CavlcParams(C.Structure):
-    """x264hip_cavlc_params (include/x264hip_lookahead.h)"""
-    _fields_ = [("slice_type", C.c_int), ("n_ref0", C.c_int), ("analyse_inter", C.c_int), ("transform8x8", C.c_int), ("cqm_custom", C.c_int),
-                ("payload", C.c_void_p), ("payload_cap", C.c_int), ("payload_len", C.c_void_p), ("mb_bits", C.c_void_p), ("slice_qp", C.c_int)]
-
-
-class ChainCavlc(C.Structure):
-    """x264hip_chain_cavlc: one chain's slice in a launch of x264hip_cavlc_write_chains"""
-    _fields_ = [("chain", C.c_int), ("state", C.c_void_p), ("params", C.c_void_p)]
-
-
 PAYLOAD_LEAD = 64
 MB_BYTES_MAX = 8192          # SW_MB_BYTES_MAX (csrc/slice_kernel.h): the sweep stops before a macroblock whose worst case might not fit
 MB_BYTES_AVG = 800           # what the default payload buffer provides per macroblock
 LL_MB_BYTES = 6144           # ... for a lossless chain below the RD levels: no I_PCM candidate caps a macroblock there (derived beside SW_MB_BYTES_MAX)
-
-
-class SliceParams(C.Structure):
-    _fields_ = [("slice_type", C.c_int), ("qp", C.c_int), ("chroma_qp_offset", C.c_int),
-                ("me_method", C.c_int), ("me_range", C.c_int), ("subme", C.c_int), ("chroma_me", C.c_int), ("mv_range", C.c_int),
-                ("fast_pskip", C.c_int), ("dct_decimate", C.c_int), ("cabac", C.c_int), ("transform8x8", C.c_int),
-                ("analyse_inter", C.c_int), ("analyse_intra", C.c_int),
-                ("quant4_mf", C.c_void_p), ("quant4_bias", C.c_void_p), ("quant8_mf", C.c_void_p), ("quant8_bias", C.c_void_p),
-                ("dequant4_mf", C.c_void_p), ("dequant8_mf", C.c_void_p),
-                ("cost_mv", C.c_void_p), ("cost_mv_range", C.c_int), ("poc", C.c_int), ("ref_poc", C.c_int * 8),
-                ("mixed_refs", C.c_int), ("profile", C.c_void_p), ("noise_reduction", C.c_int), ("nr", C.c_void_p), ("lossless", C.c_int),
-                ("rd", C.c_void_p), ("lowres_mv", C.c_void_p), ("b", C.c_void_p)]
-
-
-class NrState(C.Structure):
-    """x264hip_nr_state: h->nr_residual_sum / nr_count / nr_offset of every chain (device)."""
-    _fields_ = [("sum", C.c_void_p), ("count", C.c_void_p), ("offset", C.c_void_p)]
 
 
 def bframe_qp(qp, pb_factor=1.3):
@@ -112,7 +57,7 @@ class DeviceState:
     def __init__(self, ctx, levels=True):
         self.ctx, self.st = ctx, MbState()
         # levels=False: X264HIP_STATE_NO_LEVELS -- no coefficient-level arrays (2/3 of a state's bytes), for sweeps that write the payload themselves
-        ctx.check(ctx.lib.x264hip_mb_state_alloc_ex(ctx.h, C.byref(self.st), C.c_int(0 if levels else 1)), "mb_state_alloc")
+        ctx.check(ctx.lib.x264hip_mb_state_alloc_ex(ctx.h, C.byref(self.st), 0 if levels else 1), "mb_state_alloc")
 
     def get(self, name):
         d, B = self.ctx.dims, self.ctx.batch
@@ -120,7 +65,7 @@ class DeviceState:
         _, dt, tail = next(f for f in STATE_FIELDS if f[0] == name)
         shape = (B, 8, n, 2) if name == "mvr" else (B, n) + tail
         out = np.zeros(shape, dt)
-        rc = self.ctx.lib.x264hip_memcpy_d2h(out.ctypes.data_as(C.c_void_p), C.c_void_p(getattr(self.st, name)), C.c_size_t(out.nbytes))
+        rc = self.ctx.lib.x264hip_memcpy_d2h(out.ctypes.data_as(C.c_void_p), getattr(self.st, name), out.nbytes)
         assert rc == 0
         return out
 
@@ -176,7 +121,7 @@ class ChainEncoder:
             # p_cost_mv of every QP and the unquant tables, built by the library's host C (x264hip_cost_mv_table / _unquant_table)
             tabs = np.zeros((52, 2 * COST_SPAN + 1), np.int16)
             for q in range(52):
-                lib.x264hip_cost_mv_table(C.c_int(LAMBDA_TAB[q]), C.c_int(COST_SPAN), tabs[q].ctypes.data_as(C.c_void_p))
+                lib.x264hip_cost_mv_table(LAMBDA_TAB[q], COST_SPAN, tabs[q].ctypes.data_as(C.c_void_p))
             rb["cost_mv_all"] = DeviceArray(lib, tabs.shape, np.int16, tabs)
             if "unquant4_mf" in cqm:                   # tables from frame.cqm_init (x264hip_cqm_init): complete
                 u4, u8 = np.ascontiguousarray(cqm["unquant4_mf"], np.int32), np.ascontiguousarray(cqm["unquant8_mf"], np.int32)
@@ -184,8 +129,8 @@ class ChainEncoder:
                 q4 = np.ascontiguousarray(cqm["quant4_mf"][:, 6:12, :].astype(np.int32))       # the shift is zero at qp 6..11 (4x4) / 0..5 (8x8)
                 q8 = np.ascontiguousarray(cqm["quant8_mf"][:, 0:6, :].astype(np.int32))
                 u4, u8 = np.zeros((4, 52, 16), np.int32), np.zeros((2, 52, 64), np.int32)
-                lib.x264hip_unquant_table(q4.ctypes.data_as(C.c_void_p), C.c_int(4), C.c_int(16), u4.ctypes.data_as(C.c_void_p))
-                lib.x264hip_unquant_table(q8.ctypes.data_as(C.c_void_p), C.c_int(2), C.c_int(64), u8.ctypes.data_as(C.c_void_p))
+                lib.x264hip_unquant_table(q4.ctypes.data_as(C.c_void_p), 4, 16, u4.ctypes.data_as(C.c_void_p))
+                lib.x264hip_unquant_table(q8.ctypes.data_as(C.c_void_p), 2, 64, u8.ctypes.data_as(C.c_void_p))
             rb["unquant4_mf"] = DeviceArray(lib, u4.shape, np.int32, u4)
             rb["unquant8_mf"] = DeviceArray(lib, u8.shape, np.int32, u8)
             # x264hip_slice_rd.stale: the motion-cache entry that survives macroblocks and frames (read when temporal direct prediction
@@ -259,7 +204,7 @@ class ChainEncoder:
     def cost_table(self, qp):
         if qp not in self.cost:                        # p_cost_mv of this QP from the library's host C (x264hip_cost_mv_table), as cost_mv_all
             tab = np.zeros(2 * COST_SPAN + 1, np.int16)
-            self.lib.x264hip_cost_mv_table(C.c_int(LAMBDA_TAB[qp]), C.c_int(COST_SPAN), tab.ctypes.data_as(C.c_void_p))
+            self.lib.x264hip_cost_mv_table(LAMBDA_TAB[qp], COST_SPAN, tab.ctypes.data_as(C.c_void_p))
             self.cost[qp] = DeviceArray(self.lib, tab.shape, np.int16, tab)
         return self.cost[qp]
 
@@ -339,19 +284,19 @@ class ChainEncoder:
             self.lane_i += 1
             c, recon, state = lane["ctx"], lane["recon"], lane["state"]
             if self.anchor_ev:
-                L.x264hip_stream_wait_event(C.c_void_p(c.stream), C.c_void_p(self.anchor_ev))
+                L.x264hip_stream_wait_event(c.stream, self.anchor_ev)
         else:
             pic_i = next(i for i, p in enumerate(self.pool) if not any(p is q for q in used))
             recon, state = self.pool[pic_i], self.states[pic_i]
             keep = []
             for ev, reads in self.b_readers:       # B frames on the lanes that still read the picture / state about to be overwritten
                 if pic_i in reads:
-                    L.x264hip_stream_wait_event(C.c_void_p(c.stream), C.c_void_p(ev))
+                    L.x264hip_stream_wait_event(c.stream, ev)
                     reads.discard(pic_i)
                 if reads:
                     keep.append((ev, reads))
                 else:
-                    L.x264hip_event_destroy(C.c_void_p(ev))
+                    L.x264hip_event_destroy(ev)
             self.b_readers = keep
         refs, refs1 = self.ref_lists(self.refs, poc, stype)
         qp = iframe_qp(o["qp"]) if idr else bframe_qp(o["qp"]) if is_b else o["qp"]      # (lossless: ip_factor = 1, and QP 0 stays 0 under the default's clamp)
@@ -361,7 +306,7 @@ class ChainEncoder:
             rb, ro = dict(self.rd_bufs, **lane["bufs"]) if lane else self.rd_bufs, self.rd_opt
             self.last_bufs = rb
             if ro["aq_mode"]:                  # x264_adaptive_quant_frame on the source (R/encoder/encoder.c:1421)
-                c.check(L.x264hip_adaptive_quant_frame(c.h, C.byref(fenc), C.c_float(ro["aq_strength"]), rb["aq_energy"].p, rb["aq_offset"].p), "adaptive_quant_frame")
+                c.check(L.x264hip_adaptive_quant_frame(c.h, C.byref(fenc), ro["aq_strength"], rb["aq_energy"].p, rb["aq_offset"].p), "adaptive_quant_frame")
             self.rd = self.slice_rd(rb, float(qp), self.i_frame, rb["aq_offset"].ptr if ro["aq_mode"] else None, ro["write"], self.i_frame_stride)
             p.rd = C.addressof(self.rd)
         if is_b:
@@ -376,11 +321,11 @@ class ChainEncoder:
         ev = None
         if self.events is not None:            # HIP events on the launch stream around the sweep kernel (bench.py)
             ev = (L.x264hip_event_create(), L.x264hip_event_create())
-            L.x264hip_event_record(C.c_void_p(ev[0]), C.c_void_p(c.stream))
+            L.x264hip_event_record(ev[0], c.stream)
         c.check(L.x264hip_slice_sweep_frame(c.h, C.byref(fenc), arr, len(refs), C.byref(recon), C.byref(p), l0, C.byref(state.st)),
                 "slice_sweep_frame")
         if ev:
-            L.x264hip_event_record(C.c_void_p(ev[1]), C.c_void_p(c.stream))
+            L.x264hip_event_record(ev[1], c.stream)
             self.events.append((ev[0], ev[1], stype, len(refs) + len(refs1)))
         if self.cavlc:                                 # x264_macroblock_write_cavlc for every macroblock of every chain, from the state just written
             rb = self.last_bufs if self.raster else self.rd_bufs       # (a B frame on a lane: the lane's payload buffers)
@@ -393,7 +338,7 @@ class ChainEncoder:
             c.check(L.x264hip_noise_reduction_update(c.h, C.byref(self.nr), o["noise_reduction"]), "noise_reduction_update")
         if lane:                               # whoever overwrites one of the pictures this frame reads waits for it
             ev = L.x264hip_event_create()
-            L.x264hip_event_record(C.c_void_p(ev), C.c_void_p(c.stream))
+            L.x264hip_event_record(ev, c.stream)
             reads = {i for i, p in enumerate(self.pool) if any(p is r[0] for r in refs + refs1)}
             self.b_readers.append((ev, reads))
         self.last = (recon, state)
@@ -413,9 +358,9 @@ class ChainEncoder:
         del self.refs[self.dpb:]
         if self.lanes:                         # the point the B frames that predict from this anchor wait for
             if self.anchor_ev:
-                L.x264hip_event_destroy(C.c_void_p(self.anchor_ev))
+                L.x264hip_event_destroy(self.anchor_ev)
             self.anchor_ev = L.x264hip_event_create()
-            L.x264hip_event_record(C.c_void_p(self.anchor_ev), C.c_void_p(c.stream))
+            L.x264hip_event_record(self.anchor_ev, c.stream)
         self.t += 1
         self.i_frame += 1
 
@@ -430,9 +375,9 @@ class ChainEncoder:
         """Enqueue, behind the sweep just launched, the copy of chain b's payload length and of the first `nbytes` bytes of its payload
         into pinned host memory (x264hip_host_alloc): no synchronisation, the bytes are there once the stream has passed this point."""
         rb = getattr(self, "last_bufs", None) or self.rd_bufs
-        st = C.c_void_p(self.last_ctx.stream)
-        self.lib.x264hip_memcpy_d2h_async(C.c_void_p(host_len), C.c_void_p(rb["payload_len"].ptr + 4 * b), C.c_size_t(4), st)
-        self.lib.x264hip_memcpy_d2h_async(C.c_void_p(host_buf), C.c_void_p(rb["payload"].ptr + self.payload_cap * b + PAYLOAD_LEAD), C.c_size_t(nbytes), st)
+        st = self.last_ctx.stream
+        self.lib.x264hip_memcpy_d2h_async(host_len, rb["payload_len"].ptr + 4 * b, 4, st)
+        self.lib.x264hip_memcpy_d2h_async(host_buf, rb["payload"].ptr + self.payload_cap * b + PAYLOAD_LEAD, nbytes, st)
 
     def status(self):
         c = self.ctx
@@ -444,9 +389,9 @@ class ChainEncoder:
 
     def close(self):
         for ev, _ in self.b_readers:
-            self.lib.x264hip_event_destroy(C.c_void_p(ev))
+            self.lib.x264hip_event_destroy(ev)
         if self.anchor_ev:
-            self.lib.x264hip_event_destroy(C.c_void_p(self.anchor_ev))
+            self.lib.x264hip_event_destroy(self.anchor_ev)
         self.b_readers, self.anchor_ev = [], None
         if self.nr:
             self.lib.x264hip_nr_state_free(self.ctx.h, C.byref(self.nr))

@@ -20,14 +20,9 @@ import sys
 import numpy as np
 
 from . import lookahead as LA
+from .abi import CavlcParams, ChainCavlc, ChainSweep, MbState, SliceB
 from .frame import DeviceArray
-from .slice import COST_SPAN, CavlcParams, ChainCavlc, ChainEncoder, MbState, SLICE_B, SLICE_I, SLICE_P, SliceB
-
-
-class ChainSweep(C.Structure):
-    """x264hip_chain_sweep"""
-    _fields_ = [("chain", C.c_int), ("fenc", C.c_void_p), ("refs", C.c_void_p), ("n_refs", C.c_int), ("recon", C.c_void_p),
-                ("params", C.c_void_p), ("l0", C.c_void_p), ("out", C.c_void_p)]
+from .slice import COST_SPAN, ChainEncoder, SLICE_B, SLICE_I, SLICE_P
 
 
 class Coded:
@@ -87,7 +82,7 @@ class StreamEncoder(ChainEncoder):
             for st_ in self.states:
                 st_.ctx = self.ctx
             old.close()
-            self.ctx.check(lib.x264hip_frame_ctx_set_b_stream(self.ctx.h, C.c_void_p(sb_)), "frame_ctx_set_b_stream")
+            self.ctx.check(lib.x264hip_frame_ctx_set_b_stream(self.ctx.h, sb_), "frame_ctx_set_b_stream")
         self._hp_stream = None
         if lookahead_priority:
             self._hp_stream = lib.x264hip_stream_create_high_priority()
@@ -109,13 +104,13 @@ class StreamEncoder(ChainEncoder):
         self.c_last_idr = [0] * B
         self.c_coded = [0] * B
         tb = lib.x264hip_chain_sweep_bytes()
-        self.tab_host = lib.x264hip_host_alloc(C.c_size_t(tb * B))
+        self.tab_host = lib.x264hip_host_alloc(tb * B)
         self.tab_dev = DeviceArray(lib, (tb * B,), np.uint8)
         self.elems_dev = [DeviceArray(lib, (B,), np.int32) for _ in range(len(self.pool))]
         self.cv_host, self.cv_dev, self._cv = None, None, []       # the table of x264hip_cavlc_write_chains; what _entry notes for it
         if self.cavlc:
             cvb = lib.x264hip_chain_cavlc_bytes()
-            self.cv_host = lib.x264hip_host_alloc(C.c_size_t(cvb * B))
+            self.cv_host = lib.x264hip_host_alloc(cvb * B)
             self.cv_dev = DeviceArray(lib, (cvb * B,), np.uint8)
         self.flushing = False
         self.coded_now = [None] * B
@@ -242,7 +237,7 @@ class StreamEncoder(ChainEncoder):
                 sc[0] += int(fs[ci][0]); sc[1] += int(fs[ci][1])
             self._dscore_pending = []
         # (c.sync: the previous step's sweep and filters are done: their tables, element lists and pictures are free)
-        out, keep, filt, ev = self._launch(c, todo, C.c_void_p(self.tab_host), self.tab_dev.p, self._publish_elements, c.sync)
+        out, keep, filt, ev = self._launch(c, todo, self.tab_host, self.tab_dev.p, self._publish_elements, c.sync)
         if ev:
             px = self.ctx.dims.mb_w * 16 * self.ctx.dims.lines_y
             # per frame the source (1.5 B/px), each reference's four luma planes + chroma (4.5 B/px) and the reconstruction (1.5 B/px)
@@ -294,19 +289,19 @@ class StreamEncoder(ChainEncoder):
         ev = None
         if self.sweep_events is not None:
             ev = (L.x264hip_event_create(), L.x264hip_event_create())
-            L.x264hip_event_record(C.c_void_p(ev[0]), C.c_void_p(c.stream))
+            L.x264hip_event_record(ev[0], c.stream)
         if done_events:
-            c.check(L.x264hip_slice_sweep_chains_events(c.h, entries, len(pairs), tab_host, tab_dev, C.c_void_p(done_events[0]),
-                                                        C.c_void_p(done_events[1])), "slice_sweep_chains_events")
+            c.check(L.x264hip_slice_sweep_chains_events(c.h, entries, len(pairs), tab_host, tab_dev, done_events[0],
+                                                        done_events[1]), "slice_sweep_chains_events")
         else:
             c.check(L.x264hip_slice_sweep_chains(c.h, entries, len(pairs), tab_host, tab_dev), "slice_sweep_chains")
         if ev:
-            L.x264hip_event_record(C.c_void_p(ev[1]), C.c_void_p(c.stream))
+            L.x264hip_event_record(ev[1], c.stream)
         if self.cavlc:                                     # every chain's slice from the state its sweep just wrote: I, P and B chains in one launch
             cv = (ChainCavlc * len(self._cv))()
             for k, (ci, mine, cp) in enumerate(self._cv):
                 cv[k] = ChainCavlc(ci, C.addressof(mine), C.addressof(cp))
-            c.check(L.x264hip_cavlc_write_chains(c.h, cv, len(self._cv), C.c_void_p(self.cv_host), self.cv_dev.p), "cavlc_write_chains")
+            c.check(L.x264hip_cavlc_write_chains(c.h, cv, len(self._cv), self.cv_host, self.cv_dev.p), "cavlc_write_chains")
         if self.nr:                                        # x264_noise_reduction_update at the end of every frame (encoder.c:1755)
             c.check(L.x264hip_noise_reduction_update(c.h, C.byref(self.nr), self.opt["noise_reduction"]), "noise_reduction_update")
         for pic_i, chains in filt.items():
@@ -410,7 +405,7 @@ class StreamEncoder(ChainEncoder):
         if self.aq_slots:
             c, L, ro = self.src_ctx, self.lib, self.rd_opt
             en, off = self.aq_slots[self.look.slot(frame)]
-            c.check(L.x264hip_adaptive_quant_frame(c.h, C.byref(pic), C.c_float(ro["aq_strength"]), en.p, off.p), "adaptive_quant_frame")
+            c.check(L.x264hip_adaptive_quant_frame(c.h, C.byref(pic), ro["aq_strength"], en.p, off.p), "adaptive_quant_frame")
 
     def payloads(self):
         """slice_data() of the frame each chain coded in the last step (None where it coded nothing); valid after sync()."""
@@ -433,15 +428,15 @@ class StreamEncoder(ChainEncoder):
         for a in [self.tab_dev] + self.elems_dev + (self.stats_dev or []) + ([self.dscore_dev] if self.dscore_dev else []) + ([self.cv_dev] if self.cv_dev else []):
             a.free()
         if self.cv_host:
-            self.lib.x264hip_host_free(C.c_void_p(self.cv_host))
+            self.lib.x264hip_host_free(self.cv_host)
             self.cv_host = None
         if self.tab_host:
-            self.lib.x264hip_host_free(C.c_void_p(self.tab_host))
+            self.lib.x264hip_host_free(self.tab_host)
             self.tab_host = None
         super().close()
         self.src_ctx.close()
         if self._hp_stream:
-            self.lib.x264hip_stream_destroy(C.c_void_p(self._hp_stream))
+            self.lib.x264hip_stream_destroy(self._hp_stream)
             self._hp_stream = None
 
 
@@ -480,8 +475,8 @@ class AsyncStreamEncoder(StreamEncoder):
             lc = FrameCtx(lib, width, height, batch=B)
             # (element lists in pinned host memory, read by the filter kernels in place: with the device kept full, even a tiny upload's copy
             # kernel would wait for a wave slot)
-            self.lctx.append(dict(ctx=lc, tab_host=lib.x264hip_host_alloc(C.c_size_t(tb * B)), tab_dev=DeviceArray(lib, (tb * B,), np.uint8),
-                                  elems=[lib.x264hip_host_alloc(C.c_size_t(4 * B)) for _ in range(len(self.pool))],
+            self.lctx.append(dict(ctx=lc, tab_host=lib.x264hip_host_alloc(tb * B), tab_dev=DeviceArray(lib, (tb * B,), np.uint8),
+                                  elems=[lib.x264hip_host_alloc(4 * B) for _ in range(len(self.pool))],
                                   ev_ip=lib.x264hip_event_create(), ev_b=lib.x264hip_event_create(), busy=False, ip=[], b=[], keep=None))
         # a chain's next frame may be launched while the copy of its previous payload is still queued: two sets of what a frame writes
         d = self.ctx.dims
@@ -518,11 +513,11 @@ class AsyncStreamEncoder(StreamEncoder):
         length and first nbytes payload bytes into pinned host memory; valid once c's stream has passed this point (run() returns after that)."""
         from .slice import PAYLOAD_LEAD
         rb = self.payload_bufs(index, cd.chain)
-        st = C.c_void_p(c.stream)
+        st = c.stream
         if cd.slice_type == SLICE_B:                     # the B kernel runs on the library's second stream of this context
-            self.lib.x264hip_stream_wait_event(st, C.c_void_p(ev_b))
-        self.lib.x264hip_memcpy_d2h_async(C.c_void_p(host_len), C.c_void_p(rb["payload_len"].ptr + 4 * cd.chain), C.c_size_t(4), st)
-        self.lib.x264hip_memcpy_d2h_async(C.c_void_p(host_buf), C.c_void_p(rb["payload"].ptr + self.payload_cap * cd.chain + PAYLOAD_LEAD), C.c_size_t(nbytes), st)
+            self.lib.x264hip_stream_wait_event(st, ev_b)
+        self.lib.x264hip_memcpy_d2h_async(host_len, rb["payload_len"].ptr + 4 * cd.chain, 4, st)
+        self.lib.x264hip_memcpy_d2h_async(host_buf, rb["payload"].ptr + self.payload_cap * cd.chain + PAYLOAD_LEAD, nbytes, st)
 
     # -- pictures --------------------------------------------------------------------------------------------------------------------
     def _oldest_needed(self):
@@ -544,7 +539,7 @@ class AsyncStreamEncoder(StreamEncoder):
         self.look.prepare(f)
         # what says "picture f is in place" to the sweeps that will read it (they run on other streams)
         ev = self.pic_events.pop(f - self.n_slots, None) or self.lib.x264hip_event_create()
-        self.lib.x264hip_event_record(C.c_void_p(ev), C.c_void_p(self.src_ctx.stream))
+        self.lib.x264hip_event_record(ev, self.src_ctx.stream)
         self.pic_events[f] = ev
         self.prepared += 1
         return True
@@ -613,7 +608,7 @@ class AsyncStreamEncoder(StreamEncoder):
                 if not lc["busy"]:
                     continue
                 for kind in ("b", "ip"):
-                    if lc[kind] and L.x264hip_event_query(C.c_void_p(lc["ev_" + kind])) == 1:
+                    if lc[kind] and L.x264hip_event_query(lc["ev_" + kind]) == 1:
                         for ci in lc[kind]:
                             self.inflight_frame[ci] = -1
                             self.ncoded[ci] += 1
@@ -658,16 +653,16 @@ class AsyncStreamEncoder(StreamEncoder):
 
             def publish(pic_i, chains):                  # the launch's own list for that picture, in pinned host memory
                 np.ctypeslib.as_array(C.cast(lc["elems"][pic_i], C.POINTER(C.c_int32)), (B,))[:len(chains)] = chains
-                return C.c_void_p(lc["elems"][pic_i])
+                return lc["elems"][pic_i]
 
             def wait_pictures():
                 # the pictures these sweeps read were prepared on the lookahead's stream: wait (on the device) for the ones that may not be finished
                 for f in {fr.frame for _, fr in pairs}:
                     ev = self.pic_events.get(f)
-                    if ev is not None and L.x264hip_event_query(C.c_void_p(ev)) != 1:
-                        L.x264hip_stream_wait_event(C.c_void_p(c.stream), C.c_void_p(ev))
+                    if ev is not None and L.x264hip_event_query(ev) != 1:
+                        L.x264hip_stream_wait_event(c.stream, ev)
 
-            out, keep, filt, ev = self._launch(c, pairs, C.c_void_p(lc["tab_host"]), lc["tab_dev"].p, publish, wait_pictures, (lc["ev_ip"], lc["ev_b"]))
+            out, keep, filt, ev = self._launch(c, pairs, lc["tab_host"], lc["tab_dev"].p, publish, wait_pictures, (lc["ev_ip"], lc["ev_b"]))
             for cd in out:
                 self.coded_all[cd.chain].append(cd)
             if ev:
@@ -677,7 +672,7 @@ class AsyncStreamEncoder(StreamEncoder):
             if on_launch is not None:
                 on_launch(out, c, lc["ev_b"])            # e.g. copies of the payloads just produced (a B chain's: behind ev_b)
             # the kept frames' chains are free when the filters are done: the event that says so is recorded behind them
-            L.x264hip_event_record(C.c_void_p(lc["ev_ip"]), C.c_void_p(c.stream))
+            L.x264hip_event_record(lc["ev_ip"], c.stream)
             lc["busy"], lc["keep"] = True, keep
             lc["ip"] = [cd.chain for cd in out if cd.slice_type != SLICE_B]
             lc["b"] = [cd.chain for cd in out if cd.slice_type == SLICE_B]
@@ -709,9 +704,9 @@ class AsyncStreamEncoder(StreamEncoder):
         for lc in self.lctx:
             lc["tab_dev"].free()
             for hp in [lc["tab_host"]] + lc["elems"]:
-                self.lib.x264hip_host_free(C.c_void_p(hp))
+                self.lib.x264hip_host_free(hp)
             for e in (lc["ev_ip"], lc["ev_b"]):
-                self.lib.x264hip_event_destroy(C.c_void_p(e))
+                self.lib.x264hip_event_destroy(e)
             lc["ctx"].close()
         self.lctx = []
         super().close()

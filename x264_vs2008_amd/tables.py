@@ -1,4 +1,4 @@
-"""ctypes mirrors of include/x264hip_tables.h -- the six x264 DSP tables.
+"""ctypes mirrors of include/x264hip_tables.h -- the six x264 DSP tables (registered in abi.RECORDS beside the records of the other headers).
 
 The layouts restate R/common/pixel.h:63-103, dct.h:89-124, quant.h:26-44,
 mc.h:31-77, predict.h:27-29 and frame.h:94-108 (R/ =
@@ -8,6 +8,8 @@ can be driven through :class:`TableSet` with identical calling code, which is
 what makes the parity tests read like the reference's checkasm.
 """
 import ctypes as C
+
+from .abi import RECORDS
 
 u8p = C.POINTER(C.c_uint8)
 i16p = C.POINTER(C.c_int16)
@@ -138,6 +140,9 @@ class DeblockTable(C.Structure):
         ("deblock_v_chroma_intra", DEBLOCK_INTRA), ("deblock_h_chroma_intra", DEBLOCK_INTRA),
     ]
 
+
+RECORDS.update({"x264hip_pixel_function_t": PixelTable, "x264hip_dct_function_t": DctTable, "x264hip_zigzag_function_t": ZigzagTable, "x264hip_run_level_t": RunLevel,
+                "x264hip_quant_function_t": QuantTable, "x264hip_mc_functions_t": McTable, "x264hip_deblock_function_t": DeblockTable})
 
 PIXEL_W = (16, 16, 8, 8, 8, 4, 4, 4, 2, 2)
 PIXEL_H = (16, 8, 16, 8, 4, 8, 4, 2, 4, 2)
