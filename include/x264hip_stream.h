@@ -7,6 +7,8 @@
  *                                 the psy-RD shift of the chroma QP offset; then x264_sps_init / x264_pps_init's derived values (set.c:77-212,367-431)
  *   x264hip_param2string          x264_param2string( p, 0 ) (R/common/common.c:816-909)
  *   x264hip_sps_write / _pps_write / _sei_version_write      x264_sps_write, x264_pps_write, x264_sei_version_write (set.c:215-365,433-506), as RBSP bytes
+ *   x264hip_stat_* / x264hip_frame_report_*      h->stat: x264_fdec_filter_row's PSNR / SSIM measurement and x264_slice_write's counters per frame (device),
+ *                                 x264_encoder_frame_end's sums and x264_encoder_close's report (host C) -- at the end of this file
  *   x264hip_slice_nal             x264_slice_header_write (encoder.c:168-299) + bs_align_1 and the CABAC bytes, or the CAVLC bits spliced on
  *                                 behind the header's last bit + bs_rbsp_trailing (encoder.c:1151-1282), through x264_nal_encode
  *
@@ -80,6 +82,80 @@ int x264hip_slice_nal(const x264hip_encoder_params *p, const x264hip_slice_heade
 typedef struct x264hip_frame_stat { int64_t intra_cost, inter_cost; int32_t mbs_analysed, mb_i, mb_p, mb_skip; } x264hip_frame_stat;
 int x264hip_frame_stats(x264hip_frame_ctx *c, const x264hip_mb_state *st, x264hip_frame_stat *out_dev);
 int x264hip_scenecut_post(const x264hip_frame_stat *s, int i_mb, int i_gop_size, int scenecut_threshold, int keyint_min, int keyint_max);
+
+/* x264hip_slice_nal, which also returns in *rbsp_size the NAL's payload size before x264_nal_encode (slice header + slice data + trailing bits, no
+ * NAL header, no emulation prevention): nal->i_payload, the i_frame_size x264_encoder_encode reports and its statistics add up (encoder.c:1335,1762). */
+int x264hip_slice_nal_sized(const x264hip_encoder_params *p, const x264hip_slice_header *sh, const uint8_t *payload, int payload_len,
+                            uint8_t *dst, int cap, int *rbsp_size);
+
+/* ---- what x264 core 66 measures of every coded frame, and the report x264_encoder_close prints --------------------------------------------------
+ * Device half: one pass per step over the finished pictures and the states the sweeps left.  x264_fdec_filter_row measures while it filters
+ * (encoder.c:1031-1056): PSNR's squared error of the three planes over the true width x height, and SSIM of the luma plane from column 2 -- per
+ * macroblock row, each call's float added into the double h->stat.frame.f_ssim.  A row's later neighbours never touch rows already measured, so the
+ * finished frame gives the same numbers: measure a kept frame after x264hip_deblock_frame, a disposable B frame on its unfiltered reconstruction
+ * (b_deblock &= b_hpel, encoder.c:991), and before anything overwrites the source or the reconstruction.  ssd equals the reference's as integers and
+ * ssim as a double, bit for bit: the float adds are nested as x264_pixel_ssim_wxh and x264_fdec_filter_row nest them (csrc/frame_quality.hip).
+ * The counters are h->stat.frame's (x264_slice_write, encoder.c:1229-1251) from the state's mb_type / partition / sub_partition / ref / ref1 / cbp /
+ * t8 / qp arrays; qp_sum / (mb_w * mb_h) in float is fdec->f_qp_avg_aq (ratecontrol.c:931,1092). */
+typedef struct x264hip_frame_report {
+    int64_t ssd[3];                    /* h->stat.frame.i_ssd */
+    double  ssim;                      /* h->stat.frame.f_ssim: the sum, not yet divided by the number of 4x4 windows */
+    int32_t qp_sum;
+    int32_t mb_count[19];              /* by macroblock type (R/common/macroblock.h:61-86) */
+    int32_t mb_partition[17];          /* by partition / sub-partition type (:112-138) */
+    int32_t mb_count_8x8dct[2];
+    int32_t mb_count_ref[2][32];
+    int32_t reserved;
+} x264hip_frame_report;
+/* One chain's frame in a launch of x264hip_frame_report_chains, in the style of x264hip_chain_sweep: the pictures and the state are the batch-wide ones,
+ * the entry reads element fenc_element of the source picture, element recon_element of the reconstruction and element `chain` of the state's arrays
+ * (state NULL: no counters, they are left zero).  count_refs: param.i_frame_reference > 1. */
+typedef struct x264hip_chain_report {
+    int chain;
+    const x264hip_picture *fenc;
+    int fenc_element;
+    const x264hip_picture *recon;
+    int recon_element;
+    const x264hip_mb_state *state;
+    int slice_type;                    /* 0 P, 1 B (list 1's references are counted too), 2 I */
+    int psnr, ssim, count_refs;
+} x264hip_chain_report;
+/* out_dev: n records in entry order (device, stream-ordered).  staging_host (pinned) and table_dev: n * x264hip_chain_report_bytes() each; scratch_dev:
+ * n * x264hip_frame_report_scratch_bytes(c) (the calls' partial results); all left alone until the stream has passed the call.  Two launches on the
+ * context's stream however many entries and pictures, no synchronisation, no allocation.  Refused: a width whose two rows of block sums exceed 64 KB of LDS. */
+int x264hip_frame_report_chains(x264hip_frame_ctx *c, const x264hip_chain_report *entries, int n, void *staging_host, void *table_dev, void *scratch_dev,
+                                x264hip_frame_report *out_dev);
+size_t x264hip_chain_report_bytes(void);
+size_t x264hip_frame_report_scratch_bytes(const x264hip_frame_ctx *c);
+/* Lock step: every element of the batch from one source picture, one reconstruction and one state; out_dev [batch] records in element order.
+ * flags: X264HIP_REPORT_*.  staging_host: batch * x264hip_frame_report_frame_staging_bytes(); table_dev and scratch_dev as above with n = batch. */
+#define X264HIP_REPORT_PSNR 1
+#define X264HIP_REPORT_SSIM 2
+#define X264HIP_REPORT_REFS 4          /* param.i_frame_reference > 1 */
+int x264hip_frame_report_frame(x264hip_frame_ctx *c, const x264hip_picture *fenc, const x264hip_picture *recon, const x264hip_mb_state *state,
+                               int slice_type, int flags, void *staging_host, void *table_dev, void *scratch_dev, x264hip_frame_report *out_dev);
+size_t x264hip_frame_report_frame_staging_bytes(void);
+
+/* Host half (no device call inside): h->stat of x264_encoder_frame_end (encoder.c:1760-1835) in the reference's types -- double sums, int64_t counts,
+ * the float x264_psnr -- and x264_encoder_close's report (encoder.c:1899-2080).  psnr / ssim: param.analyse.b_psnr / b_ssim; both are forced off when
+ * the parameters are lossless, as x264_validate_parameters does (encoder.c:410-411).  p: validated parameters (x264hip_validate_parameters). */
+typedef struct x264hip_stat x264hip_stat;
+typedef struct x264hip_stat_frame {
+    int slice_type;                    /* 0 P, 1 B, 2 I */
+    int frame_size;                    /* h->out.i_frame_size: x264hip_slice_nal_sized's rbsp_size */
+    int nal_ref_idc, poc;              /* printed in the per-frame line */
+    int frames_since_ref;              /* P: fdec->i_frame - fref0[0]->i_frame - 1, the B frames before this P in display order */
+    int direct_spatial;                /* B: sh.b_direct_spatial_mv_pred */
+} x264hip_stat_frame;
+x264hip_stat *x264hip_stat_new(const x264hip_encoder_params *p, int psnr, int ssim);
+void x264hip_stat_delete(x264hip_stat *s);
+/* One coded frame (not a given-up attempt of the post-encode scene cut: x264_encoder_frame_end never sees those).  Writes the X264_LOG_DEBUG line
+ * "x264 [debug]: frame=%4d QP=%.2f NAL=%d Slice:%c Poc:%-3d I:%-4d P:%-4d SKIP:%-4d size=%d bytes PSNR Y:... SSIM Y:...\n" into line (may be NULL);
+ * returns its length, or -1. */
+int x264hip_stat_frame_end(x264hip_stat *s, const x264hip_stat_frame *f, const x264hip_frame_report *r, char *line, int cap);
+/* x264_encoder_close's lines in order, each as x264_log's default handler prints it ("x264 [info]: ...\n"); returns the length, or -1 if cap is too small. */
+int x264hip_stat_summary(const x264hip_stat *s, char *dst, int cap);
+int x264hip_stat_frames(const x264hip_stat *s);        /* frames accumulated so far */
 
 #ifdef __cplusplus
 }

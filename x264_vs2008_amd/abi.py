@@ -184,6 +184,23 @@ class SliceHeader(C.Structure):
                 ("poc", C.c_int), ("qp", C.c_int), ("n_ref0", C.c_int), ("n_ref1", C.c_int), ("direct_spatial", C.c_int), ("ref_frame_num", C.c_int * 16)]
 
 
+class FrameReport(C.Structure):
+    """What the quality pass leaves per coded frame: h->stat.frame's measurements and counters."""
+    _fields_ = [("ssd", C.c_int64 * 3), ("ssim", C.c_double), ("qp_sum", C.c_int32), ("mb_count", C.c_int32 * 19), ("mb_partition", C.c_int32 * 17),
+                ("mb_count_8x8dct", C.c_int32 * 2), ("mb_count_ref", (C.c_int32 * 32) * 2), ("reserved", C.c_int32)]
+
+
+class ChainReport(C.Structure):
+    """One chain's frame in a launch of x264hip_frame_report_chains."""
+    _fields_ = [("chain", C.c_int), ("fenc", C.c_void_p), ("fenc_element", C.c_int), ("recon", C.c_void_p), ("recon_element", C.c_int),
+                ("state", C.c_void_p), ("slice_type", C.c_int), ("psnr", C.c_int), ("ssim", C.c_int), ("count_refs", C.c_int)]
+
+
+class StatFrame(C.Structure):
+    _fields_ = [("slice_type", C.c_int), ("frame_size", C.c_int), ("nal_ref_idc", C.c_int), ("poc", C.c_int), ("frames_since_ref", C.c_int),
+                ("direct_spatial", C.c_int)]
+
+
 # C typedef name -> record; tables.py adds the seven of include/x264hip_tables.h
 RECORDS = {"x264hip_cfg": Cfg, "x264hip_frame_dims": Dims, "x264hip_picture": Picture, "x264hip_cqm_tables": CqmTables,
            "x264hip_me_params": MeParams, "x264hip_me16_params": Me16Params, "x264hip_mb_state": MbState, "x264hip_slice_rd": SliceRd,
@@ -191,7 +208,8 @@ RECORDS = {"x264hip_cfg": Cfg, "x264hip_frame_dims": Dims, "x264hip_picture": Pi
            "x264hip_deblock_params": DeblockParams, "x264hip_lookahead_params": LookaheadParams, "x264hip_look_need": Need,
            "x264hip_look_frame": Frame, "x264hip_look_slot": LookSlot, "x264hip_look_task": LookTask, "x264hip_look_params": LookParams,
            "x264hip_chain_sweep": ChainSweep, "x264hip_cavlc_params": CavlcParams, "x264hip_chain_cavlc": ChainCavlc,
-           "x264hip_encoder_params": EncoderParams, "x264hip_slice_header": SliceHeader}
+           "x264hip_encoder_params": EncoderParams, "x264hip_slice_header": SliceHeader, "x264hip_frame_report": FrameReport,
+           "x264hip_chain_report": ChainReport, "x264hip_stat_frame": StatFrame}
 
 
 # Every function the three headers declare, as "return:parameters" in the classes the declarations use --
@@ -311,4 +329,15 @@ PROTOTYPES = {
     "x264hip_slice_nal": "i:pppipi",
     "x264hip_frame_stats": "i:ppp",
     "x264hip_scenecut_post": "i:piiiii",
+    "x264hip_slice_nal_sized": "i:pppipip",
+    "x264hip_frame_report_chains": "i:ppipppp",
+    "x264hip_chain_report_bytes": "z:",
+    "x264hip_frame_report_scratch_bytes": "z:p",
+    "x264hip_frame_report_frame": "i:ppppiipppp",
+    "x264hip_frame_report_frame_staging_bytes": "z:",
+    "x264hip_stat_new": "p:pii",
+    "x264hip_stat_delete": "v:p",
+    "x264hip_stat_frame_end": "i:ppppi",
+    "x264hip_stat_summary": "i:ppi",
+    "x264hip_stat_frames": "i:p",
 }

@@ -19,6 +19,7 @@
 #include <cstring>
 #include "device_prims.h"
 #include "intra_pred.h"
+#include "ssim_dev.h"
 #include "internal.h"
 
 using namespace x264hip;
@@ -164,14 +165,10 @@ __global__ __launch_bounds__(256) void k_l1(L1Args a, u8 *arena)
     case OP_SSIM_CORE: {
         if (tid < 2) {
             const u8 *p1 = arena + a.off[0] + 4 * tid, *p2 = arena + a.off[1] + 4 * tid;
-            u32 s1 = 0, s2 = 0, ss = 0, s12 = 0;
-            for (int y = 0; y < 4; y++)
-                for (int x = 0; x < 4; x++) {
-                    int u = p1[y * 8 + x], v = p2[y * 8 + x];
-                    s1 += u; s2 += v; ss += u * u + v * v; s12 += u * v;
-                }
-            int *o = (int *)(arena + a.off[9]) + 4 * tid;
-            o[0] = s1; o[1] = s2; o[2] = ss; o[3] = s12;
+            int o[4];
+            ssim_4x4_sums(p1, 8, p2, 8, o);
+            int *dst = (int *)(arena + a.off[9]) + 4 * tid;
+            for (int k = 0; k < 4; k++) dst[k] = o[k];
         }
         break;
     }
@@ -179,16 +176,11 @@ __global__ __launch_bounds__(256) void k_l1(L1Args a, u8 *arena)
         // float; summed strictly left to right as R/common/pixel.c:458-468 does
         if (tid == 0) {
             const int *s0 = (const int *)(arena + a.off[0]), *s1 = (const int *)(arena + a.off[1]);
-            const int c1 = 416, c2 = 235963;   // (int)(.01*.01*255*255*64+.5), (int)(.03*.03*255*255*64*63+.5)
             float acc = 0.0f;
             for (int i = 0; i < a.p[0]; i++) {
                 int t[4];
                 for (int k = 0; k < 4; k++) t[k] = s0[4 * i + k] + s0[4 * i + 4 + k] + s1[4 * i + k] + s1[4 * i + 4 + k];
-                int vars = t[2] * 64 - t[0] * t[0] - t[1] * t[1];
-                int covar = t[3] * 64 - t[0] * t[1];
-                float num = __fmul_rn((float)(2 * t[0] * t[1] + c1), (float)(2 * covar + c2));
-                float den = __fmul_rn((float)(t[0] * t[0] + t[1] * t[1] + c1), (float)(vars + c2));
-                acc = __fadd_rn(acc, __fdiv_rn(num, den));
+                acc = __fadd_rn(acc, ssim_end1(t[0], t[1], t[2], t[3]));
             }
             *(float *)(arena + a.off[9]) = acc;
         }

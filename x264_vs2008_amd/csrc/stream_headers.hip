@@ -332,8 +332,8 @@ extern "C" int x264hip_sei_version_write(const x264hip_encoder_params *p, uint8_
     return s.bytes();
 }
 
-extern "C" int x264hip_slice_nal(const x264hip_encoder_params *p, const x264hip_slice_header *sh, const uint8_t *payload, int payload_len,
-                                 uint8_t *dst, int cap)
+static int slice_nal(const x264hip_encoder_params *p, const x264hip_slice_header *sh, const uint8_t *payload, int payload_len,
+                     uint8_t *dst, int cap, int *rbsp_size)
 {
     NEED_VALID(p, "slice_nal");
     if (payload_len < 0 || (payload_len && !payload)) { set_error("slice_nal: no payload"); return -1; }
@@ -416,6 +416,19 @@ extern "C" int x264hip_slice_nal(const x264hip_encoder_params *p, const x264hip_
     }
     if (s.over) { free(rbsp); set_error("slice_nal: header does not fit"); return -1; }
     const int n = x264hip_nal_encode(dst, 1, sh->nal_ref_idc, sh->nal_type, rbsp, s.bytes());
+    if (rbsp_size) *rbsp_size = s.bytes();
     free(rbsp);
     return n;
+}
+extern "C" int x264hip_slice_nal(const x264hip_encoder_params *p, const x264hip_slice_header *sh, const uint8_t *payload, int payload_len,
+                                 uint8_t *dst, int cap)
+{
+    return slice_nal(p, sh, payload, payload_len, dst, cap, nullptr);
+}
+// the same, and the size of the NAL's payload before x264_nal_encode (header + slice data + trailing bits: nal->i_payload, what
+// x264_encoder_encode adds up as h->out.i_frame_size, encoder.c:1335)
+extern "C" int x264hip_slice_nal_sized(const x264hip_encoder_params *p, const x264hip_slice_header *sh, const uint8_t *payload, int payload_len,
+                                       uint8_t *dst, int cap, int *rbsp_size)
+{
+    return slice_nal(p, sh, payload, payload_len, dst, cap, rbsp_size);
 }

@@ -20,12 +20,15 @@ given at once are coded as chains of one batch.
 Readers: raw I420 (R/muxers.c:63-122: frame i at i * w * h * 3 / 2) and YUV4MPEG2 (:124-316: W, H, F from the stream header, C420* only, every
 FRAME header skipped to its newline).  Refused, never approximated: what the library refuses (x264hip_validate_parameters, the encoders' own
 checks) -- ABR / VBV / 2-pass, --direct none, --no-cabac with --subme 6 and above (the RD levels), interlaced, threads > 1, b-pyramid.
+Every coded frame is measured as x264 does by default (PSNR, SSIM, macroblock statistics: --no-psnr / --no-ssim / --quiet turn that off, -v prints
+x264_encoder_frame_end's line per frame) and x264_encoder_close's report goes to stderr at the end, one per stream; the `.264` bytes do not depend on it.
 Scene cuts work as in the reference: by default after the fact (a P picture that should have been intra is coded again, encoder.c:1603-1699), with
 --pre-scenecut in the lookahead."""
 import argparse
 import os
 import re
 import sys
+import time
 
 import numpy as np
 
@@ -86,8 +89,10 @@ def build_parser():
     a("--level", default=None, help="4.1 / 41 ...")
     a("--threads", type=int, default=1)
     a("--no-asm", action="store_true", help="accepted and ignored (there is no asm here)")
-    a("--no-psnr", action="store_true", help="accepted and ignored")
-    a("--no-ssim", action="store_true", help="accepted and ignored")
+    a("--no-psnr", action="store_true", help="disable PSNR computation")
+    a("--no-ssim", action="store_true", help="disable SSIM computation")
+    a("--quiet", action="store_true", help="quiet mode: no statistics (a log level below INFO turns both measurements off, R/encoder/encoder.c:587-591)")
+    a("-v", "--verbose", action="store_true", help="print stats for each frame")
     a("--device", type=int, default=0, help="GPU to run on")
     return ap
 
@@ -125,6 +130,12 @@ def param_fields(o):
         lv = o.level
         k["level_idc"] = int(10 * float(lv) + .5) if "." in lv or int(lv) < 6 else int(lv)
     return k
+
+
+def report_fields(o):
+    """param.analyse.b_psnr / b_ssim and the log level as the command line leaves them: both measurements are x264's defaults (R/common/common.c:131-132),
+    --no-psnr / --no-ssim turn one off, --quiet (X264_LOG_NONE) both and the report with them; -v (X264_LOG_DEBUG) adds the per-frame line."""
+    return dict(psnr=int(not o.no_psnr and not o.quiet), ssim=int(not o.no_ssim and not o.quiet), verbose=bool(o.verbose and not o.quiet), quiet=bool(o.quiet))
 
 
 # ---- readers (R/muxers.c) ----------------------------------------------------------------------------------------------------------------
@@ -219,9 +230,29 @@ def check_built(p):
                          "(--subme 5 and below are)" % p.subpel_refine)
 
 
-def encode_streams(lib, p, sources, n_frames, sinks):
-    """p: validated parameters (mux.encoder_params); sources: readers of equal picture size; sinks: binary files, one per source."""
+def encode_streams(lib, p, sources, n_frames, sinks, psnr=0, ssim=0, verbose=False, stats=None, observe=None):
+    """p: validated parameters (mux.encoder_params); sources: readers of equal picture size; sinks: binary files, one per source.
+    psnr / ssim: measure every coded frame (x264hip_frame_report_*); stats: a list that receives one quality.Stat per stream (the caller prints
+    its summary and closes it); verbose: x264_encoder_frame_end's line per frame on stderr; observe(enc, chain, frame, slice type, picture, state,
+    muxer): called for every accounted frame while its reconstruction and state are still on the device (a checker's view of what was measured)."""
     check_built(p)
+    from .quality import Stat
+    if stats is not None:
+        stats += [Stat(lib, p, psnr, ssim) for _ in sources]
+    measure = dict(psnr=psnr, ssim=ssim, mb_stats=1) if stats is not None else {}
+    last_anchor = [None] * len(sources)
+
+    def account(b, record, stype, frame, direct_spatial=1, where=None):
+        """x264_encoder_frame_end for stream b's frame, from what its muxer just wrote."""
+        m = muxers[b].last
+        if observe is not None:
+            observe(enc, b, frame, stype, where[0], where[1], muxers[b])
+        since = 0 if last_anchor[b] is None else frame - last_anchor[b] - 1
+        line = stats[b].frame_end(record, stype, m["frame_size"], nal_ref_idc=m["nal_ref_idc"], poc=m["poc"], frames_since_ref=since, direct_spatial=direct_spatial)
+        if stype != sl.SLICE_B:
+            last_anchor[b] = frame
+        if verbose:
+            sys.stderr.write(("%s: " % getattr(sinks[b], "name", b) if len(sources) > 1 else "") + line)
     from .frame import JVT_LISTS, cqm_init
     from . import slice as sl
     B, w, h = len(sources), p.width, p.height
@@ -238,7 +269,7 @@ def encode_streams(lib, p, sources, n_frames, sinks):
     coded = 0
     if not needs_lookahead(p):
         # x264_slicetype_decide has nothing to decide: an IDR every keyint frames, P frames between, constant QP
-        enc = sl.ChainEncoder(lib, w, h, cq, batch=B, write=1, **common)
+        enc = sl.ChainEncoder(lib, w, h, cq, batch=B, write=1, **common, **measure)
         try:
             for t in range(n_frames):
                 for b, s in enumerate(sources):
@@ -247,8 +278,14 @@ def encode_streams(lib, p, sources, n_frames, sinks):
                 enc.status()
                 pays = enc.payloads()
                 enc.finish_frame()
+                recs = None
+                if stats is not None:
+                    enc.sync()
+                    recs = enc.reports()
                 for b in range(B):
                     sinks[b].write(muxers[b].frame(frame=t, ftype=mux.TYPE_IDR if stype == sl.SLICE_I else mux.TYPE_P, qp=qp, payload=pays[b]))
+                    if recs is not None:
+                        account(b, recs[b], stype, t, where=enc.last)
                 coded += 1
         finally:
             enc.close()
@@ -257,7 +294,7 @@ def encode_streams(lib, p, sources, n_frames, sinks):
     enc = StreamEncoder(lib, w, h, cq, batch=B, n_frames=n_frames, crf=p.rf_constant if p.rc_method == mux.RC_CRF else None, b_adapt=p.bframe_adaptive,
                         bframe_bias=p.bframe_bias, keyint_min=p.keyint_min, scenecut_threshold=p.scenecut_threshold, pre_scenecut=p.pre_scenecut,
                         ip_factor=p.ip_factor, pb_factor=p.pb_factor, qcompress=p.qcompress, qp_step=p.qp_step, bframes=p.bframe, weightb=p.weighted_bipred,
-                        direct_pred=p.direct_mv_pred, **common)
+                        direct_pred=p.direct_mv_pred, **common, **measure)
 
     def fill(pic, f):
         for b, s in enumerate(sources):
@@ -275,6 +312,8 @@ def encode_streams(lib, p, sources, n_frames, sinks):
                 for cd in out:
                     sinks[cd.chain].write(muxers[cd.chain].frame(frame=cd.frame, ftype=cd.type, qp=cd.qp, payload=pays[cd.chain], n_ref0=cd.n_ref0, n_ref1=cd.n_ref1,
                                                                  direct_spatial=cd.direct_spatial, frame_num_reset=cd.frame_num_reset))
+                    if stats is not None:
+                        account(cd.chain, enc.report_of(cd), cd.slice_type, cd.frame, cd.direct_spatial, where=(enc.pool[cd.pic], enc.states[cd.pic]))
                     coded += 1
     finally:
         enc.close()
@@ -314,13 +353,23 @@ def main(argv=None):
         raise SystemExit("encode: several inputs need an output pattern with %d")
     names = [o.output % i if "%d" in o.output else o.output for i in range(len(sources))]
     sinks = [open(nm, "wb") for nm in names]
+    rf = report_fields(o)
+    stats = None if rf["quiet"] else []
+    t0 = time.time()
     try:
-        done = encode_streams(lib, p, sources, n, sinks)
+        done = encode_streams(lib, p, sources, n, sinks, psnr=rf["psnr"], ssim=rf["ssim"], verbose=rf["verbose"], stats=stats)
     except (ValueError, RuntimeError) as ex:
         raise SystemExit("encode: " + str(ex))
     finally:
         for s in sinks:
             s.close()
+    dt = max(time.time() - t0, 1e-6)
+    # x264_encoder_close's report per stream, then the command line's own last line (R/x264.c:890-897: the file's bytes over the clip's duration)
+    for b, st in enumerate(stats or []):
+        pre = "%s: " % names[b] if len(sources) > 1 else ""
+        sys.stderr.write("".join(pre + ln + "\n" for ln in st.summary().splitlines()))
+        sys.stderr.write("%sencoded %d frames, %.2f fps, %.2f kb/s\n" % (pre, done, done / dt, float(os.path.getsize(names[b])) * 8 * p.fps_num / (float(p.fps_den) * done * 1000)))
+        st.close()
     print("encoded %d frames of %d stream%s (%dx%d): %s" % (done, len(sources), "" if len(sources) == 1 else "s", w, h, ", ".join(names)), file=sys.stderr)
     return 0
 

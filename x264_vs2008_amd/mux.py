@@ -80,6 +80,7 @@ class AnnexB:
         self.lib, self.p = lib, params
         self.frame_num, self.idr_pic_id, self.last_idr = 0, 0, 0
         self.refs = []                     # [(poc, frame_num)] of the pictures kept as references since the last IDR
+        self.last = None                   # the last slice's numbers for the statistics
 
     def frame(self, frame, ftype, qp, payload, n_ref0=None, n_ref1=None, direct_spatial=1, frame_num_reset=False):
         """All NALs of one x264_encoder_encode call: `frame` is the picture's input number, `ftype` its X264_TYPE_*, `qp` the slice QP,
@@ -114,10 +115,13 @@ class AnnexB:
             sh.ref_frame_num[i] = r[1]
         cap = len(payload) * 3 // 2 + 64
         buf = C.create_string_buffer(cap)
-        n = lib.x264hip_slice_nal(C.byref(p), C.byref(sh), payload, len(payload), buf, cap)
+        size = C.c_int(0)
+        n = lib.x264hip_slice_nal_sized(C.byref(p), C.byref(sh), payload, len(payload), buf, cap, C.byref(size))
         if n < 0:
             raise ValueError("x264hip_slice_nal: " + _err(lib))
         out += buf.raw[:n]
+        # what x264_encoder_frame_end reports of this frame (quality.Stat.frame_end): h->out.i_frame_size, the slice's type, nal_ref_idc and POC
+        self.last = dict(frame_size=size.value, slice_type=sh.slice_type, nal_ref_idc=sh.nal_ref_idc, poc=sh.poc)
         if sh.nal_ref_idc != PRIORITY_DISPOSABLE:
             self.refs.append((sh.poc, self.frame_num))
             self.refs = sorted(self.refs, key=lambda r: -r[0])[:p.d_num_ref_frames]

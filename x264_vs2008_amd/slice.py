@@ -11,6 +11,7 @@ import math
 import numpy as np
 
 from .abi import STATE_FIELDS, CavlcParams, ChainCavlc, DeblockParams, MbState, NrState, SliceB, SliceParams, SliceRd
+from . import quality
 from .frame import LAMBDA_TAB, CqmDevice, DeviceArray, FrameCtx
 
 SLICE_P, SLICE_B, SLICE_I = 0, 1, 2
@@ -80,9 +81,15 @@ class ChainEncoder:
                  transform8x8=0, fast_pskip=1, dct_decimate=1, chroma_me=1, cabac=0, deblock=0, alpha_c0=0, beta=0,
                  chroma_qp_offset=0, keyint=0, mixed_refs=0, noise_reduction=0, mv_range=0,
                  trellis=0, psy_rd=0.0, aq_mode=0, aq_strength=1.0, write=0, cabac_init_idc=0, qp_min=0, qp_max=51, payload_cap=0, raster=None,
-                 bframes=0, weightb=0, direct_pred=1, lanes=0, levels=True):
+                 bframes=0, weightb=0, direct_pred=1, lanes=0, levels=True, psnr=0, ssim=0, mb_stats=0):
         self.lib = lib
         self.lossless = int(qp == 0)
+        # param.analyse.b_psnr / b_ssim: the quality pass (quality.py) behind every frame -- a B frame's behind its sweep, on its unfiltered
+        # reconstruction, a kept frame's behind the loop filter (x264_fdec_filter_row measures what it has just filtered, and b_deblock &= b_hpel).
+        # mb_stats: the pass for h->stat.frame's counters alone (x264 counts macroblock types whether or not it measures).  Off by default: quality is
+        # None and nothing is enqueued.  Lossless turns the two measurements off (R/encoder/encoder.c:410-411)
+        self.quality = quality.flags(psnr and not self.lossless, ssim and not self.lossless, n_refs) if psnr or ssim or mb_stats else None
+        self.reporters, self.last_report = {}, None
         if self.lossless:              # x264_validate_parameters, R/encoder/encoder.c:401-429: what constant QP 0 turns off (CQP: no adaptive quantisation)
             fast_pskip, noise_reduction, chroma_qp_offset, trellis, psy_rd, aq_mode = 0, 0, 0, 0, 0.0, 0
             transform8x8 = int(bool(transform8x8 and cabac))
@@ -343,7 +350,23 @@ class ChainEncoder:
             self.b_readers.append((ev, reads))
         self.last = (recon, state)
         self.last_ctx = c
+        self.last_src, self.last_stype = fenc, stype
+        if is_b and self.quality is not None:              # a disposable B frame is never filtered: measured as the sweep left it, on the stream it ran on
+            self.measure(c, fenc, recon, state, stype)
         return stype, qp, state
+
+    def measure(self, c, fenc, recon, state, stype):
+        """The quality pass for the frame just coded, enqueued on context c (the main one or a lane's); reports() reads it after the sync."""
+        if id(c) not in self.reporters:
+            self.reporters[id(c)] = quality.Reporter(c, c.batch)
+        self.last_report = self.reporters[id(c)].frame(fenc, recon, state.st, stype, self.quality)
+
+    def reports(self):
+        """x264hip_frame_report of the last frame of every chain (valid after sync(); a kept frame's after finish_frame): a numpy record
+        array [batch] of quality.REPORT_DTYPE -- ssd, ssim (f_ssim, not yet divided), qp_sum and h->stat.frame's counters."""
+        if self.last_report is None:
+            raise RuntimeError("no quality pass was enqueued: ChainEncoder(psnr=1 / ssim=1), and finish_frame() for a kept frame")
+        return quality.Reporter.records(self.last_report)
 
     def finish_frame(self):
         """x264_fdec_filter_row for the whole frame: loop filter, borders, half-pel planes; then the frame joins the reference list."""
@@ -354,6 +377,8 @@ class ChainEncoder:
             self.i_frame += 1
             return
         self.filter_kept(c, recon, state.st)
+        if self.quality is not None:           # behind the loop filter, before the next upload overwrites the source
+            self.measure(c, self.last_src, recon, state, self.last_stype)
         self.refs.insert(0, (recon, state, getattr(self, "last_poc", 2 * (self.t - self.last_idr))))
         del self.refs[self.dpb:]
         if self.lanes:                         # the point the B frames that predict from this anchor wait for
@@ -393,6 +418,9 @@ class ChainEncoder:
         if self.anchor_ev:
             self.lib.x264hip_event_destroy(self.anchor_ev)
         self.b_readers, self.anchor_ev = [], None
+        for r in self.reporters.values():
+            r.close()
+        self.reporters = {}
         if self.nr:
             self.lib.x264hip_nr_state_free(self.ctx.h, C.byref(self.nr))
             self.nr = None

@@ -20,6 +20,7 @@ import sys
 import numpy as np
 
 from . import lookahead as LA
+from . import quality
 from .abi import CavlcParams, ChainCavlc, ChainSweep, MbState, SliceB
 from .frame import DeviceArray
 from .slice import COST_SPAN, ChainEncoder, SLICE_B, SLICE_I, SLICE_P
@@ -27,7 +28,7 @@ from .slice import COST_SPAN, ChainEncoder, SLICE_B, SLICE_I, SLICE_P
 
 class Coded:
     """What one chain coded in a step."""
-    __slots__ = ("chain", "frame", "type", "slice_type", "qp", "f_qpm", "poc", "n_ref0", "n_ref1", "i_satd", "frame_num_reset", "direct_spatial")
+    __slots__ = ("chain", "frame", "type", "slice_type", "qp", "f_qpm", "poc", "n_ref0", "n_ref1", "i_satd", "frame_num_reset", "direct_spatial", "report", "pic")
 
     def __repr__(self):
         return "Coded(chain=%d frame=%d type=%d qp=%d poc=%d)" % (self.chain, self.frame, self.type, self.qp, self.poc)
@@ -136,6 +137,9 @@ class StreamEncoder(ChainEncoder):
                                  "(the reference's has too, but per frame, not per batch); run with pre_scenecut=1")
             self.stats_dev = [DeviceArray(lib, (B, 32), np.uint8) for _ in self.pool]
         self.sweep_events = None       # set to [] to collect (start, stop, chains, algorithmic bytes) HIP events around every step's sweep launches
+        # psnr / ssim (ChainEncoder's options): ONE quality pass per launch over the chains that coded a frame, behind the kept frames' loop filter
+        # (the B frames' reconstructions stay unfiltered), every entry naming its chain's source slot, pool picture and state (quality.Reporter.chains)
+        self._q, self._reporter = [], None
 
     # ---- one call of x264_encoder_encode for every chain --------------------------------------------------------------------------
     def _prepare(self, fill):
@@ -275,7 +279,7 @@ class StreamEncoder(ChainEncoder):
         the two timing events around the launch if self.sweep_events collects them."""
         L = self.lib
         keep, written, filt, out = [], set(), {}, []
-        self._cv = []
+        self._cv, self._q = [], []
         entries = (ChainSweep * len(pairs))()
         for k, (ci, fr) in enumerate(pairs):
             entries[k], cd, pic_i = self._entry(ci, fr, keep)
@@ -308,7 +312,22 @@ class StreamEncoder(ChainEncoder):
             c.check(L.x264hip_frame_ctx_elements(c.h, publish(pic_i, chains), len(chains)), "frame_ctx_elements")
             self.filter_kept(c, self.pool[pic_i], self.states[pic_i].st)
         c.check(L.x264hip_frame_ctx_elements(c.h, None, 0), "frame_ctx_elements")
+        if self.quality is not None:                       # x264_fdec_filter_row's measurement and x264_slice_write's counters, all chains in one enqueue
+            if done_events:
+                raise ValueError("psnr / ssim: a launch whose B kernel ends on a stream of its own is not measured (StreamEncoder and ChainEncoder are)")
+            if self._reporter is None:
+                self._reporter = quality.Reporter(c, c.batch)
+            ps, ss, rf = self.quality & quality.REPORT_PSNR, self.quality & quality.REPORT_SSIM, self.quality & quality.REPORT_REFS
+            h = self._reporter.chains([(ci, self.look.pics[slot], ci, self.pool[pic_i], ci, mine, stype, ps, ss, rf) for ci, slot, pic_i, mine, stype in self._q])
+            for k, cd in enumerate(out):
+                cd.report = (h, k)
         return out, keep, filt, ev
+
+    def report_of(self, cd):
+        """The x264hip_frame_report (a quality.REPORT_DTYPE record) of a Coded this encoder returned; valid after sync(), until 8 further launches."""
+        if cd.report is None:
+            raise RuntimeError("no quality pass was enqueued: StreamEncoder(psnr=1 / ssim=1)")
+        return quality.Reporter.records(cd.report[0])[cd.report[1]]
 
     def _scenecut_hits(self):
         """After sync(): the chains whose P picture of the last sweep the reference would give up (encoder.c:1603-1644)."""
@@ -389,6 +408,9 @@ class StreamEncoder(ChainEncoder):
         cd.n_ref0, cd.n_ref1, cd.i_satd = len(refs), len(refs1), fr.i_satd
         cd.frame_num_reset = int(getattr(fr, "frame_num_reset", 0))
         cd.direct_spatial = dsp
+        cd.report = None
+        cd.pic = pic_i                                 # the pool picture (and state) this frame was coded into
+        self._q.append((ci, slot, pic_i, mine, stype))
         self._undo[ci] = (list(refs_all), self.c_coded[ci])
         self.coded_now[ci] = cd
         if stype != SLICE_B:                           # kept: filtered below, then this chain's newest reference
@@ -420,6 +442,9 @@ class StreamEncoder(ChainEncoder):
     def close(self):
         self.sync()
         self.src_ctx.sync()
+        if self._reporter is not None:
+            self._reporter.close()
+            self._reporter = None
         self.lb.close()
         self.look.close()
         for pair in self.aq_slots or []:
@@ -493,6 +518,9 @@ class AsyncStreamEncoder(StreamEncoder):
         self.pic_events = {}                             # per picture number: what says "in place" to the sweeps that read it (_prepare_picture)
         self.coded_all = [[] for _ in range(B)]          # per chain: the Coded records of its frames, in coding order
         self.next_frame, self.cost_batches, self.undecided = {}, [], set()
+        if self.quality is not None:
+            raise ValueError("AsyncStreamEncoder: psnr / ssim: a launch's B kernel ends on a stream of its own and its chains move on at once; the quality "
+                             "pass is enqueued per step (StreamEncoder) or per frame (ChainEncoder)")
         if self.cavlc:
             raise ValueError("AsyncStreamEncoder: cabac=0: the CAVLC pass follows a step's whole sweep on one stream (StreamEncoder); here a launch's B kernel "
                              "ends on a stream of its own")
