@@ -20,11 +20,19 @@ import numpy as np
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 from oracle import hostpic  # noqa: E402
 from x264_vs2008_amd import synth  # noqa: E402
 
 CASES = [((352, 288), 1, 0, 0, 0, 18, 44), ((200, 120), 2, 3, -2, 2, 8, 51)]
+# pictures of one to six macroblocks (tests/edge_cases.py: SIZES), whose padding is wider than the picture.  synth.frame cannot make them; each
+# size is paired with the content kind of edge_cases.content() on which the reference's loop filter changes at least 16 luma pixels (main()
+# asserts it).  That is "ramp" at every size: on pure 0 / 255 noise ("satnoise") no edge passes the alpha / beta thresholds and the filter
+# changes 0 or 1 pixels, which would pin nothing.
+TINY_CONTENT = {(16, 16): "ramp", (32, 16): "ramp", (16, 32): "ramp", (48, 16): "ramp", (16, 48): "ramp", (24, 24): "ramp", (18, 18): "ramp", (40, 24): "ramp"}
+TINY_MIN_CHANGED = 16
+CASES += [(size, 12, 3, -2, 2, 8, 51) for size in TINY_CONTENT]          # (seed 12: QPs high enough at every size for the filter to act on the ramp)
 
 
 class RefFrame(C.Structure):
@@ -57,7 +65,11 @@ def make_case(size, seed, qlo, qhi):
     g = hostpic.Geometry(*size)
     n = g.mb_w * g.mb_h
     r = np.random.RandomState(seed)
-    y, u, v = synth.frame(size[0], size[1], seed)
+    if max(size) < 65:
+        import edge_cases
+        y, u, v = (a[0] for a in edge_cases.content(TINY_CONTENT[size], size[0], size[1], 1))
+    else:
+        y, u, v = synth.frame(size[0], size[1], seed)
     y, u, v = blocky(blocky(y, r, 4, 3), r, 16, 6), blocky(u, r, 4, 4), blocky(v, r, 4, 4)
     mb_type = r.choice([0, 0, 0, 1, 2, 3], n).astype(np.uint8)
     qp = r.randint(qlo, qhi + 1, n).astype(np.uint8)
@@ -259,6 +271,7 @@ def main():
         for nm in ("y", "u", "v", "h", "vv", "c"):
             out["rec." + nm] = rec.arr(nm).copy()
         changed = int((rec.visible("y")[:size[1], :size[0]] != inp["y"]).sum())
+        assert size not in TINY_CONTENT or changed >= TINY_MIN_CHANGED, "%dx%d %s: the loop filter changed %d luma pixels" % (size + (TINY_CONTENT[size], changed))
         name = "frame_drivers_%dx%d.npz" % size
         np.savez_compressed(os.path.join(ROOT, "tests", "golden", name), offsets=np.array([a_off, b_off, c_off]),
                             **{"in." + k: v for k, v in inp.items()}, **{"out." + k: v for k, v in out.items()})

@@ -1,0 +1,109 @@
+"""GPU: every variant of the macroblock sweep on pictures of one to six macroblocks (tests/edge_cases.py: mb_w x mb_h of 1x1, 2x1, 1x2,
+3x1, 1x3, 2x2 with 8 and 14 padded columns / rows, 3x2) with flat, saturated, full-range and noise content -- the geometry-dependent code
+(the wavefront's row-to-row wait, neighbour availability and the vector-predictor fallbacks behind it, the search limits and the vector
+clip, temporal direct prediction's co-located reads, the anti-diagonal loop filter, borders and half-pel planes whose padding is wider than
+the picture) and saturated residuals.  One test per (size, configuration): nine chains, one per content kind, in lock step through every
+sweep; after every frame each chain is held, bit for bit, to the CPU twin (pinned to the reference on the same chains by
+tests/test_oracle_edge_chains.py) or, where the twin does not code the configuration, to the reference's recorded digests
+(tests/golden/edge_chains.npz).  enc.status() follows every sweep, so a stalled row dependency is the spin-limit error, not a hang."""
+import ctypes as C
+import os
+
+import numpy as np
+import pytest
+
+import edge_cases as E
+from paths import GOLDEN
+from x264_vs2008_amd import slice as sl
+
+pytestmark = pytest.mark.gpu
+
+PLAIN_ARRAYS = ("mb_type", "mv", "ref", "cbp", "nnz", "luma", "chroma_ac")      # what the smoke run's wavefront step compares
+TWIN_ARRAYS = ("mb_type", "qp", "mv", "ref", "cbp")
+
+
+def kind_of(enc, stype):
+    """The kernel kind sweep_build (csrc/frame_slice.hip) selects, from what the encoder exposes."""
+    if not enc.raster:
+        return E.SW_KIND_PLAIN
+    if stype == sl.SLICE_B:
+        return E.SW_KIND_B if enc.bopt["direct_spatial"] else E.SW_KIND_BT
+    if enc.lossless:
+        return E.SW_KIND_LL_RF if enc.opt["subme"] >= 8 else E.SW_KIND_LL
+    return E.SW_KIND_RF if enc.opt["subme"] >= 8 else E.SW_KIND_RD
+
+
+def list1(enc, state, name, tail, dt):
+    out = np.zeros((enc.ctx.batch, enc.ctx.dims.mb_w * enc.ctx.dims.mb_h) + tail, dt)
+    assert enc.lib.x264hip_memcpy_d2h(out.ctypes.data_as(C.c_void_p), getattr(state.st, name), out.nbytes) == 0
+    return out
+
+
+def same(got, want, what):
+    got = got.reshape(want.shape)
+    assert np.array_equal(got, want), "%s differs first at %s" % (what, np.argwhere(got != want)[:3].tolist())
+
+
+def planes(enc, recon, b):
+    return [enc.ctx.download(recon, nm, padded=False, b=b) for nm in ("y", "u", "v")]
+
+
+@pytest.mark.parametrize("name", list(E.CONFIGS))
+@pytest.mark.parametrize("size", E.SIZES, ids=E.size_id)
+def test_tiny_picture_chains(hip_lib, oracle_lib, cqm, size, name):
+    src, kw, ekw, frames = E.CONFIGS[name]
+    kw = dict(kw)
+    if kw.pop("cqm_preset", 0):                        # --cqm jvt: the quantiser tables x264_cqm_init builds for the JVT matrices
+        with np.load(os.path.join(GOLDEN, "cqm_jvt.npz")) as z:
+            cqm = {k: z[k] for k in z.files}
+    B = len(E.CONTENTS)
+    clips = [E.clip(kind, size, frames) for kind in E.CONTENTS]
+    want = [E.twin_chain(name, size, kind) for kind in E.CONTENTS]
+    gold = [E.recorded(name, size, kind) for kind in E.CONTENTS] if src == "ref" else None
+    enc = sl.ChainEncoder(hip_lib, size[0], size[1], cqm, batch=B, write=int(src != "plain"), **kw, **(ekw or {}))
+    try:
+        for f, (disp, stype) in enumerate(E.order_of(name)):
+            for b, (y, u, v) in enumerate(clips):
+                enc.upload(y[disp], u[disp], v[disp], b=b)
+            st, qp, state = enc.encode_frame(stype=stype, disp=disp)
+            enc.status()
+            assert kind_of(enc, stype) == E.expected_kind(name, stype), "frame %d: the encoder's flags select kernel kind %d" % (f, kind_of(enc, stype))
+            got = {k: state.get(k) for k in (PLAIN_ARRAYS if src == "plain" else TWIN_ARRAYS)}
+            if stype == sl.SLICE_B:
+                got["mv1"], got["ref1"] = list1(enc, state, "mv1", (16, 2), np.int16), list1(enc, state, "ref1", (4,), np.int8)
+            pays = enc.payloads() if src != "plain" else None
+            recon = enc.last[0]
+            rec = [planes(enc, recon, b) for b in range(B)]
+            enc.finish_frame()
+            enc.sync()
+            fin = [planes(enc, recon, b) for b in range(B)] if stype != sl.SLICE_B else None
+            for b, kind in enumerate(E.CONTENTS):
+                what = "%s %dx%d chain %d (%s) frame %d (%s, display %d)" % (name, size[0], size[1], b, kind, f, "PBI"[stype], disp)
+                a = want[b]
+                if a is not None:
+                    assert (st, qp) == (int(a["frame_info"][f, 0]), int(a["frame_info"][f, 1])), "%s: (slice type, QP) %s" % (what, (st, qp))
+                if src == "ref":
+                    pay_md5, mbt_md5, _ = gold[b]
+                    # a CAVLC chain: the decisions against the twin's first, so that a failure says where
+                    for k in (E.DECISIONS if a is not None else ()):
+                        same(got[k][b], a[k][f], "%s: %s" % (what, k))
+                    assert E.md5(got["mb_type"][b]) == bytes(mbt_md5[f]), "%s: mb_type differs from the reference's" % what
+                    assert E.md5(np.frombuffer(pays[b], np.uint8)) == bytes(pay_md5[f]), "%s: payload (%d bytes) differs from the reference's" % (what, len(pays[b]))
+                else:
+                    for k in got:
+                        same(got[k][b], a[k][f], "%s: %s" % (what, k))
+                    if src == "twin":
+                        assert pays[b] == E.payload(a, f), "%s: payload differs (%d bytes, the twin %d)" % (what, len(pays[b]), int(a["payload_len"][f]))
+                if kw["qp"] == 0:                      # lossless: whatever the expected values say, the reconstruction IS the source
+                    for i, nm in enumerate("yuv"):
+                        s = clips[b][i][disp]
+                        same(rec[b][i][:s.shape[0], :s.shape[1]], s, "%s: lossless reconstruction %s against the source" % (what, nm))
+                        same(fin[b][i][:s.shape[0], :s.shape[1]], s, "%s: filtered lossless reconstruction %s against the source" % (what, nm))
+                if a is not None:
+                    for i, nm in enumerate("yuv"):
+                        if stype == sl.SLICE_B:        # a disposable B frame is never filtered
+                            same(rec[b][i], a["rec_" + nm][f], "%s: rec_%s" % (what, nm))
+                        else:                          # the new reference behind the loop filter (its borders and half-pel planes: the next frame's payload)
+                            same(fin[b][i], a["fin_" + nm][f], "%s: fin_%s" % (what, nm))
+    finally:
+        enc.close()

@@ -5,7 +5,6 @@ every decision, every level, mb_bits, the payload bytes and the planes; and, ind
 against the source.  Lock-step launches (x264hip_slice_sweep_frame), batches, and the chain table (x264hip_slice_sweep_chains).
 
 Without the lossless raster kernels every test here fails with "lossless is not built in the raster variant"."""
-import ctypes as C
 import hashlib
 import os
 
@@ -18,8 +17,8 @@ from oracle.gen_golden_slice import case_inputs
 from x264_vs2008_amd import slice as sl
 from paths import REF_SO
 from slice_util import run_chain2
+from table_util import table_launch
 from x264_vs2008_amd.frame import DeviceArray
-from x264_vs2008_amd.stream import ChainSweep
 
 pytestmark = pytest.mark.gpu
 STATE = [k for k in LC.WHOLE if k not in ("mvr", "frame_info", "stat", "payload_len", "mb_bits")]
@@ -113,62 +112,6 @@ def test_three_chains_with_different_content_in_one_launch(hip_lib, cqm):
                     assert len(d["payload"][b]) > 0
     finally:
         enc.close()
-
-
-def table_launch(hip_lib, cqm, size, frames, y, u, v, kw, qps):
-    """Every frame of a batch of len(qps) chains (all fed the same clip) through x264hip_slice_sweep_chains, chain b at QP qps[b]: one
-    ChainEncoder per QP value owns the tables of its chains, all of them share the first one's context, pictures and states.
-    Returns per frame the payloads of every chain; raises what the library refuses."""
-    B = len(qps)
-    encs = {}
-    for q in sorted(set(qps)):
-        encs[q] = sl.ChainEncoder(hip_lib, size[0], size[1], cqm, batch=B, write=1, **dict(kw, qp=q))
-    e0 = encs[qps[0]]
-    lib, c = hip_lib, e0.ctx
-    tb = lib.x264hip_chain_sweep_bytes()
-    tab_host = lib.x264hip_host_alloc(tb * B)
-    tab_dev = DeviceArray(lib, (tb * B,), np.uint8)
-    out = []
-    try:
-        for f in range(frames):
-            for b in range(B):
-                e0.upload(y[f], u[f], v[f], b=b)
-            idr = f == 0
-            if idr:
-                e0.refs = []
-            used = [r[0] for r in e0.refs]
-            pic_i = next(i for i, p in enumerate(e0.pool) if not any(p is q for q in used))
-            recon, state = e0.pool[pic_i], e0.states[pic_i]
-            refs, _ = e0.ref_lists(e0.refs, 2 * f, sl.SLICE_I if idr else sl.SLICE_P)
-            arr = (C.c_void_p * max(len(refs), 1))(*[C.addressof(r[0]) for r in refs]) if refs else None
-            entries, keep = (ChainSweep * B)(), []
-            for b in range(B):
-                e = encs[qps[b]]
-                p = e.slice_params(sl.SLICE_I if idr else sl.SLICE_P, qps[b], 2 * f, e.cost_table(qps[b]).ptr, None)
-                rd = e.slice_rd(dict(e.rd_bufs, payload=e0.rd_bufs["payload"], payload_len=e0.rd_bufs["payload_len"], mb_bits=e0.rd_bufs["mb_bits"],
-                                     stale=e0.rd_bufs["stale"]), float(qps[b]), e0.i_frame, None, 1, 0)      # (i_frame: x264_cabac_encode_flush's padding bit)
-                rd.payload_cap = e0.payload_cap
-                p.rd = C.addressof(rd)
-                for i, r in enumerate(refs):
-                    p.ref_poc[i] = r[2]
-                keep += [p, rd]
-                entries[b] = ChainSweep(chain=b, fenc=C.addressof(e0.fenc), refs=C.cast(arr, C.c_void_p) if arr else None, n_refs=len(refs),
-                                        recon=C.addressof(recon), params=C.addressof(p), l0=C.addressof(refs[0][1].st) if refs else None, out=C.addressof(state.st))
-            c.check(lib.x264hip_mb_state_clear_progress(c.h, C.byref(state.st)), "mb_state_clear_progress")
-            c.check(lib.x264hip_slice_sweep_chains(c.h, entries, B, tab_host, tab_dev.p), "slice_sweep_chains")
-            e0.last, e0.last_ctx, e0.last_bufs, e0.last_is_b, e0.last_poc = (recon, state), c, e0.rd_bufs, False, 2 * f
-            e0.status()
-            rec = [np.stack([c.download(recon, nm, padded=False, b=b) for b in range(B)]) for nm in ("y", "u", "v")]
-            out.append(dict(payload=e0.payloads(), mb_type=state.get("mb_type"), rec=rec, mb_bits=e0.rd_bufs["mb_bits"].get()))
-            e0.finish_frame()
-            c.sync()
-    finally:
-        c.sync()
-        tab_dev.free()
-        lib.x264hip_host_free(tab_host)
-        for e in encs.values():
-            e.close()
-    return out
 
 
 @pytest.mark.parametrize("name", ["s6_med", "s8_med"])
