@@ -151,6 +151,13 @@ static int sweep_build(x264hip_frame_ctx *c, const x264hip_picture *fenc, const 
         if (p->lossless && prd->trellis) { set_error("slice_sweep: lossless with trellis (x264_validate_parameters turns trellis off at QP 0)"); return -1; }
         if (p->lossless && prd->psy_rd) { set_error("slice_sweep: lossless with psy-rd (x264_validate_parameters turns psy-rd off at QP 0)"); return -1; }
         if (p->lossless && p->chroma_qp_offset) { set_error("slice_sweep: lossless with a chroma QP offset (x264_validate_parameters clears chroma_qp_offset at QP 0)"); return -1; }
+        // psy-trellis: x264_validate_parameters zeroes it at QP 0 (with psy-rd, R/encoder/encoder.c:413-414) and without trellis (:502-503)
+        if (prd->psy_trellis < 0) { set_error("slice_sweep: psy_trellis %d (h->mb.i_psy_trellis: FIX8 of the strength / 4, not negative)", prd->psy_trellis); return -1; }
+        if (p->lossless && prd->psy_trellis) { set_error("slice_sweep: lossless with psy-trellis (x264_validate_parameters turns psy-trellis off at QP 0)"); return -1; }
+        if (prd->psy_trellis && !(p->cabac && prd->trellis)) { set_error("slice_sweep: psy-trellis without trellis (x264_validate_parameters zeroes psy-trellis when trellis is off, and trellis without CABAC)"); return -1; }
+        // the reference's h->mb.pic.fenc_dct4 / fenc_dct8 outlive macroblocks and frames, and some blocks are quantised against what an earlier one left:
+        // with trellis 1 always; with trellis 2 a B slice below the RD levels reads, and an I or P slice at subme 6 writes (slice_sweep_body.h)
+        if (prd->psy_trellis && !prd->psy_carry && (prd->trellis == 1 || (is_b ? !mbrd : (mbrd && p->subme == 6)))) { set_error("slice_sweep: psy-trellis needs x264hip_slice_rd.psy_carry (in every sweep of the chain)"); return -1; }
         if (p->lossless && prd->aq_offset) { set_error("slice_sweep: lossless with adaptive quantisation (constant QP 0 has no AQ: every macroblock is coded at QP 0)"); return -1; }
         if (mbrd && (p->analyse_inter & 0x20)) { set_error("slice_sweep: sub-8x8 partitions with the RD levels not built (their partial bit counts read cache entries the previous macroblock left)"); return -1; }
         if (!out->mvd) { set_error("slice_sweep: mb_state without mvd"); return -1; }
@@ -248,7 +255,9 @@ static int sweep_build(x264hip_frame_ctx *c, const x264hip_picture *fenc, const 
         r.on = 1; r.mbrd = mbrd; r.trellis = p->cabac ? prd->trellis : 0; r.psy_rd = mbrd ? prd->psy_rd : 0;
         r.write = prd->write; r.cabac_init_idc = prd->cabac_init_idc; r.i_frame = prd->i_frame; r.i_frame_stride = prd->i_frame_stride;
         r.aq = prd->aq_offset != nullptr; r.qp_min = prd->qp_min; r.qp_max = prd->qp_max; r.chroma_qp_offset = p->chroma_qp_offset;
-        r.f_qpm = prd->f_qpm; r.aq_offset = prd->aq_offset; r.cost_mv_all = prd->cost_mv_all;
+        r.f_qpm = prd->f_qpm; r.psy_trellis = prd->psy_trellis;
+        r.psy_carry_lo = (u32)(uintptr_t)prd->psy_carry; r.psy_carry_hi = (u32)((unsigned long long)(uintptr_t)prd->psy_carry >> 32);
+        r.aq_offset = prd->aq_offset; r.cost_mv_all = prd->cost_mv_all;
         r.unq4 = prd->unquant4_mf; r.unq8 = prd->unquant8_mf;
         r.payload = prd->payload; r.payload_cap = prd->payload_cap; r.payload_len = prd->payload_len; r.mb_bits = prd->mb_bits;
         r.mvd = out->mvd;
@@ -313,6 +322,7 @@ extern "C" int x264hip_slice_sweep_frame(x264hip_frame_ctx *c, const x264hip_pic
     return 0;
 }
 
+thread_local bool sw_table_psy = false;
 // The chain-table launch: every entry is a sweep of ONE chain (batch element) with its own pictures, states and slice parameters.
 static int sweep_chains(x264hip_frame_ctx *c, x264hip_chain_sweep *e, int n, void *staging_host, void *table_dev, void *ev_ip, void *ev_b, bool join);
 static int b_events(x264hip_frame_ctx *c)
@@ -353,7 +363,7 @@ static int sweep_chains(x264hip_frame_ctx *c, x264hip_chain_sweep *e, int n, voi
     if (!staging_host || !table_dev) { set_error("slice_sweep_chains: staging / table buffers missing"); return -1; }
     SwDesc *st = (SwDesc *)staging_host;
     // entries sorted by kind (sweep_tables.h): a first pass builds, a second places
-    int cnt[SW_N_KINDS] = {0}, n_cavlc = 0;
+    int cnt[SW_N_KINDS] = {0}, n_cavlc = 0, n_psy = 0;
     static thread_local std::vector<SwDesc> tmp;
     static thread_local std::vector<int> kinds;
     tmp.resize((size_t)n); kinds.resize((size_t)n);
@@ -366,7 +376,7 @@ static int sweep_chains(x264hip_frame_ctx *c, x264hip_chain_sweep *e, int n, voi
         if (sweep_build(c, s.fenc, s.refs, s.n_refs, s.recon, s.params, s.l0, s.out, tmp[i].a, tmp[i].t, tmp[i].r, kind)) return -1;
         kind = k_sweep_kinds[kind].in_table;
         tmp[i].a.chain = s.chain;
-        kinds[i] = kind; cnt[kind]++;
+        kinds[i] = kind; cnt[kind]++; n_psy += tmp[i].r.psy_trellis != 0;
         sweep_note_frame(s.params, s.n_refs, s.out);
     }
     // one launch is all-lossless or not at all: QP 0 changes what every table and buffer of a chain means (SPS profile, payload bound,
@@ -376,6 +386,8 @@ static int sweep_chains(x264hip_frame_ctx *c, x264hip_chain_sweep *e, int n, voi
     // ... and all-CAVLC or not at all: the caller follows the launch with ONE x264hip_cavlc_write_chains over the same chains, and a CABAC
     // chain's payload slot already holds its slice then
     if (n_cavlc && n_cavlc != n) { set_error("slice_sweep_chains: %d of %d entries are CAVLC slices without a writer (cabac = 0, rd.write = 0): a chain table is all-CAVLC or not at all", n_cavlc, n); return -1; }
+    // ... and all-psy-trellis or not at all: its kernels are others (k_psy_raster), one launch per kind, and the strength is a setting of the whole encode
+    if (n_psy && n_psy != n) { set_error("slice_sweep_chains: %d of %d entries have psy-trellis on: a chain table is all-psy-trellis or not at all", n_psy, n); return -1; }
     int base[SW_N_KINDS], at[SW_N_KINDS];
     sweep_place(cnt, base);
     memcpy(at, base, sizeof(at));
@@ -392,7 +404,9 @@ static int sweep_chains(x264hip_frame_ctx *c, x264hip_chain_sweep *e, int n, voi
         HIPCHK(hipStreamWaitEvent(c->b_stream, c->b_ready, 0));
     }
     const hipStream_t b_stream = two ? c->b_stream : c->stream;
+    sw_table_psy = n_psy != 0;                         // what the launch functions cannot read from the device's table
     sweep_enqueue(tab, cnt, base, c->stream, b_stream);
+    sw_table_psy = false;
     if (two && join) {
         HIPCHK(hipEventRecord(c->b_done, c->b_stream));
         HIPCHK(hipStreamWaitEvent(c->stream, c->b_done, 0));

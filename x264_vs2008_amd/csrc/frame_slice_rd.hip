@@ -4,5 +4,6 @@
 
 void x264hip_launch_slice_rd(const SwArgs &a, const SwRefs &t, const SwRd &r, hipStream_t stream)
 {
+    if (r.psy_trellis) { x264hip_launch_psy_rd(a, t, r, stream); return; }
     hipLaunchKernelGGL((k_slice_sweep<2, false, true>), dim3((unsigned)a.batch), dim3(64), 0, stream, a, t, r, nullptr);
 }

@@ -622,6 +622,7 @@
         const int t8_bak = t8;
         PROF(6);
         if (!(fin && type == T_I_PCM)) encode_mb(fin ? 1 : 0);
+        else psy_after_analysis();
         if (fin) { encoded = true; break; }
         PROF(0);
         int cst = ssd_mb();

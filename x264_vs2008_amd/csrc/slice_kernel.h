@@ -31,6 +31,7 @@
 // references with or without mixed references (DIA / HEX / UMH, subme 0..5, chroma ME), 4x4 / 8x8 transform choice, CQP.
 // The lane id is laundered once per macroblock and at phase boundaries (LAUNDER): otherwise every lane-derived address of the
 // 60k-instruction body is hoisted out of the macroblock loop and spilled.
+#include <cstddef>
 #include <cstring>
 #include "me_exact.h"
 #include "intra_pred.h"
@@ -159,10 +160,13 @@ struct SwRd {                       // kernel argument
     int write, cabac_init_idc, i_frame, i_frame_stride;
     int aq, qp_min, qp_max, chroma_qp_offset;
     float f_qpm;
+    int psy_trellis;                // h->mb.i_psy_trellis (k_psy_raster; in what was padding: every other member keeps its offset)
     const float *aq_offset;         // [batch][n_mb]
     const i16 *cost_mv_all;         // [52][2 * cost_center + 1]: p_cost_mv of every QP
     const int *unq4, *unq8;         // h->unquant4_mf [4][52][16], h->unquant8_mf [2][52][64]
-    u8 *payload; int payload_cap; int *payload_len, *mb_bits;
+    u8 *payload; int payload_cap;
+    u32 psy_carry_lo;               // x264hip_slice_rd.psy_carry, low half (k_psy_raster; this and psy_carry_hi sit in what was padding, as psy_trellis does)
+    int *payload_len, *mb_bits;
     i16 *mvd;                       // h->mb.mvd[0]: [batch][n_mb][16][2]
     // B slices: list 1 of the per-macroblock state, h->mb.skipbp, and the co-located picture's arrays (direct prediction)
     i16 *mv1, *mvr1, *mvd1;
@@ -171,9 +175,13 @@ struct SwRd {                       // kernel argument
     const signed char *col_type, *col_ref;
     const i16 *col_mv;
     int direct_temporal;            // !sh.b_direct_spatial_mv_pred
+    u32 psy_carry_hi;
     int *direct_score;              // --direct auto: [batch][2] h->stat.frame.i_direct_score ({temporal, spatial}); NULL: off
     i16 *stale;                     // [batch][8]: the cache entry of block 12 that survives macroblocks and frames (x264hip_slice_rd.stale)
 };
+static_assert(offsetof(SwRd, psy_carry_lo) == offsetof(SwRd, payload_cap) + 4 && offsetof(SwRd, payload_len) == offsetof(SwRd, psy_carry_lo) + 4 &&
+              offsetof(SwRd, psy_carry_hi) == offsetof(SwRd, direct_temporal) + 4 && offsetof(SwRd, direct_score) == offsetof(SwRd, psy_carry_hi) + 4,
+              "the two halves of the psy-trellis carry's address fill padding: the kernel argument of every other kernel keeps its layout");
 // what a B slice adds to the wavefront's LDS: list 1 of the motion caches, the direct prediction, the analysis records
 struct SwLdsB {
     signed char cref1[48], cskip[48];
@@ -230,7 +238,19 @@ struct MbSynDev {
     i16 (*lv4)[16], (*lv8)[64], *lv_dc, (*lv_cdc)[4], (*lv_cac)[16];
 };
 // trellis context handed to the quantising helpers: on = 0 -> plain dead-zone quantisation
-struct SwTq { int on; SwLdsRd *r; };
+struct SwTq { static constexpr bool PSY = false; int on; SwLdsRd *r; };
+// ... and with psy-trellis (k_psy_raster): psy = h->mb.i_psy_trellis.
+// src4 / src8: what h->mb.pic.fenc_dct4 / fenc_dct8 hold when this macroblock's blocks are quantised -- its own source's transform, the zeros x264_t
+// was allocated with, or what an EARLIER macroblock (of this frame or of one before it) left: kept[512], the chain's slot of x264hip_slice_rd.psy_carry
+enum { SW_PSY_OWN = 0, SW_PSY_ZERO = 1, SW_PSY_KEPT = 2 };
+struct SwTqPsy { static constexpr bool PSY = true; int on; SwLdsRd *r; int psy, src4, src8; i16 *kept; };
+__device__ __forceinline__ void sw_tq_set_psy(SwTq &, int, int, i16 *) {}
+__device__ __forceinline__ void sw_tq_set_psy(SwTqPsy &tq, int psy, int src, i16 *kept) { tq.psy = psy; tq.src4 = tq.src8 = src; tq.kept = kept; }
+__device__ __forceinline__ i16 *sw_psy_carry(const SwRd &rd, int bz)
+{
+    const unsigned long long p = ((unsigned long long)rd.psy_carry_hi << 32) | rd.psy_carry_lo;
+    return p ? (i16 *)p + (size_t)bz * 512 : nullptr;
+}
 // x264_dct4_weight2_zigzag[0] / x264_dct8_weight2_zigzag[0] (R/common/dct.c:476-483) and x264_zigzag_scan4[0]
 static __device__ const int d_w4z[16] = {800, 320, 320, 800, 128, 800, 320, 320, 320, 320, 128, 800, 128, 320, 320, 128};
 static __device__ const u8 d_zz4[16] = {0, 4, 1, 2, 5, 8, 12, 9, 6, 3, 7, 10, 13, 14, 11, 15};
@@ -444,6 +464,122 @@ __device__ __forceinline__ u32 sw_modes8c(int nb, int &n)
 __device__ __forceinline__ int sw_fix16(int m) { return m < 4 ? m : 2; }      // x264_mb_pred_mode16x16_fix
 __device__ __forceinline__ int sw_fix8c(int m) { return m < 4 ? m : 0; }      // x264_mb_pred_mode8x8c_fix
 
+// ---- psy-trellis: the source block's own transform in scan order (x264_psy_trellis_init, R/encoder/analyse.c:488-507) ----
+// The reference transforms the source macroblock at most once and keeps 1 KiB of it in x264_t (h->mb.pic.fenc_dct4 [16][16], fenc_dct8 [4][64]), which it
+// never clears: a block is quantised against whatever the arrays hold.  Where that is the macroblock's own source (SW_PSY_OWN) the block(s) about to be
+// quantised are transformed again from s.fe right before the trellis, into 128 bytes of the motion search's patch behind the trellis' level lists (the
+// patch is idle while a block is quantised): no LDS is added.  Where it is what an earlier macroblock left (SW_PSY_KEPT) they come from the chain's 1 KiB
+// of global memory (x264hip_slice_rd.psy_carry: fenc_dct4 | fenc_dct8, in scan order), which sw_psy_keep4 / sw_psy_keep8 write where the reference writes
+// its arrays; where nobody ever wrote them, zeros (SW_PSY_ZERO).
+#define SW_PSY_FENC(s_) ((i16 *)((s_).patch + 16 * TDW_TREE_STRIDE))
+static_assert(4 * TDW_TREE_STRIDE >= TDW_TREE_ENTRIES && 16 * TDW_TREE_STRIDE + 128 <= MX_PATCH_BYTES, "the source coefficients sit behind the level lists");
+// x264_dct4_weight_tab / x264_dct8_weight_tab (R/common/dct.h:25-53) by raster index
+struct SwPw4 { __device__ __forceinline__ int operator[](int r) const { const int n = ((r >> 2) & 1) + (r & 1); return n == 0 ? 453 : n == 1 ? 286 : 181; } };
+struct SwPw8 {
+    __device__ __forceinline__ int operator[](int r) const
+    {
+        const int k = d_w8cls[((r >> 1) & 12) | (r & 3)];
+        return k == 0 ? 256 : k == 1 ? 227 : k == 2 ? 410 : k == 3 ? 241 : k == 4 ? 324 : 305;
+    }
+};
+__device__ __forceinline__ int sw_fwd4_quad(int v, int k);
+// x264_zigzag_scan4's position of raster coefficient l16
+__device__ __forceinline__ int sw_psy_zz4(int l16) { return (int)((0xFDC6EB75A8419320ull >> (4 * l16)) & 15); }
+// the 16-lane group of `lane` transforms the source's 4x4 block k, as sw_encode_i4x4 does the residual: lane l16 returns dct[l16] (raster)
+__device__ __forceinline__ int sw_psy_dct4(SwLds &s, int k, int lane)
+{
+    int bx, by;
+    sw_blk_xy(k, bx, by);
+    const int l16 = lane & 15, x = l16 & 3, y = l16 >> 2, tl = (lane & 48) | (x << 2) | y;
+    int v = (int)s.fe[(by + y) * 16 + bx + x];
+    v = sw_fwd4_quad(v, x);
+    v = __shfl(v, tl, 64);
+    return sw_fwd4_quad(v, x);
+}
+// the source's 8x8 block j through the 8x8 transform's intermediate (s.t8: the residual's passes are over when the trellis runs): leaves dct[r] (raster) in s.t8[64 + r]
+__device__ __forceinline__ void sw_psy_dct8(SwLds &s, int j, int lane)
+{
+    i16 *tmp = s.t8;
+    const int k8 = lane & 7;
+    if (lane < 8) {
+        const u8 *p1 = s.fe + (j >> 1) * 8 * 16 + (j & 1) * 8 + k8;
+        int v[8], o[8];
+#pragma unroll
+        for (int k = 0; k < 8; k++) v[k] = (int)p1[k * 16];
+        fwd8_1d(o, v);
+#pragma unroll
+        for (int k = 0; k < 8; k++) tmp[k * 8 + k8] = (i16)o[k];
+    }
+    WAVE_SYNC();
+    if (lane < 8) {
+        int v[8], o[8];
+#pragma unroll
+        for (int k = 0; k < 8; k++) v[k] = tmp[k8 * 8 + k];
+        fwd8_1d(o, v);
+#pragma unroll
+        for (int k = 0; k < 8; k++) tmp[64 + k * 8 + k8] = (i16)o[k];
+    }
+    WAVE_SYNC();
+}
+// every lane calls it: the source coefficients of 4x4 block k (the 16-lane group's own) into the group's 16 entries of SW_PSY_FENC
+template <class TQ>
+__device__ __forceinline__ void sw_psy_src4(SwLds &s, TQ tq, int k, int lane)
+{
+    const int l16 = lane & 15;
+    if (tq.src4 != SW_PSY_OWN) SW_PSY_FENC(s)[(lane & 48) + l16] = tq.src4 == SW_PSY_ZERO ? (i16)0 : tq.kept[k * 16 + l16];
+    else SW_PSY_FENC(s)[(lane & 48) + sw_psy_zz4(l16)] = (i16)sw_psy_dct4(s, k, lane);
+    WAVE_SYNC();
+}
+// ... and of 8x8 block j, one per lane
+template <class TQ>
+__device__ __forceinline__ void sw_psy_src8(SwLds &s, TQ tq, int j, int lane)
+{
+    if (tq.src8 != SW_PSY_OWN) SW_PSY_FENC(s)[lane] = tq.src8 == SW_PSY_ZERO ? (i16)0 : tq.kept[256 + j * 64 + lane];
+    else {
+        sw_psy_dct8(s, j, lane);
+        SW_PSY_FENC(s)[lane] = s.t8[64 + c_scan8[0][lane]];
+    }
+    WAVE_SYNC();
+}
+// x264_psy_trellis_init's two halves: the source macroblock's sixteen 4x4 transforms / four 8x8 transforms into the chain's kept arrays.  The
+// fence makes the stores visible to the lanes that read them back in a later macroblock (WAVE_SYNC orders LDS only).
+__device__ __forceinline__ void sw_psy_keep4(SwLds &s, i16 *kept, int lane)
+{
+#pragma nounroll
+    for (int it = 0; it < 4; it++) {
+        const int k = 4 * it + (lane >> 4);
+        kept[k * 16 + sw_psy_zz4(lane & 15)] = (i16)sw_psy_dct4(s, k, lane);
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+}
+__device__ __forceinline__ void sw_psy_keep8(SwLds &s, i16 *kept, int lane)
+{
+#pragma nounroll
+    for (int j = 0; j < 4; j++) {
+        sw_psy_dct8(s, j, lane);
+        kept[256 + j * 64 + lane] = s.t8[64 + c_scan8[0][lane]];
+        WAVE_SYNC();
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+}
+// x264_psy_trellis_init( h, 0 ) after the analysis (--trellis 1, analyse.c:2770-2771): ONLY the size h->mb.b_transform_8x8 (f8) names at that moment is
+// refreshed.  An inter macroblock is then coded with that size; an I_4x4 / I_16x16 one with f8 set (left by the transform decision of the inter candidate
+// it beat) and an I_8x8 one with f8 clear (the flag turns 1 only in x264_macroblock_encode, macroblock.c:533, or in x264_rd_cost_i8x8 of the
+// refinement, rdo.c:249) are quantised against what an earlier macroblock left.
+__device__ __forceinline__ void sw_psy_after_analysis(SwLds &, SwTq &, int, int) {}
+__device__ __forceinline__ void sw_psy_after_analysis(SwLds &s, SwTqPsy &tq, int f8, int lane)
+{
+    if (f8) { sw_psy_keep8(s, tq.kept, lane); tq.src8 = SW_PSY_OWN; tq.src4 = SW_PSY_KEPT; }
+    else { sw_psy_keep4(s, tq.kept, lane); tq.src4 = SW_PSY_OWN; tq.src8 = SW_PSY_KEPT; }
+}
+// x264_psy_trellis_init( h, param.analyse.b_transform_8x8 ) in x264_mb_cache_fenc_satd (--trellis 2, analyse.c:515-516)
+__device__ __forceinline__ void sw_psy_before_trials(SwLds &, SwTq &, int, int) {}
+__device__ __forceinline__ void sw_psy_before_trials(SwLds &s, SwTqPsy &tq, int both, int lane)
+{
+    if (both) sw_psy_keep8(s, tq.kept, lane);
+    sw_psy_keep4(s, tq.kept, lane);
+}
+
 // ---- encode pieces (R/encoder/macroblock.c:116-363, 596-768; no trellis, not lossless) ------------
 // luma 4x4 transform + quant + scan + dequant of the 16 blocks, lanes 0-15.  cat: 0 intra, 1 inter.
 // i16 mode takes the DC out first (s.dc16 in raster order) and scores with decimate_score15.
@@ -457,7 +593,8 @@ __device__ __forceinline__ int sw_denoise(int v, int off, int &la)
     return level < 0 ? 0 : (level ^ sign) - sign;
 }
 // mask8: the 8x8 blocks to do (x264_macroblock_encode_p8x8 codes one); lanes of other blocks leave everything of theirs alone
-__device__ __forceinline__ void sw_luma4x4_fwd(SwLds &s, const SwArgs &a, const SwQp &Q, SwTq tq, int cat, bool dc_out, int lane, int *nr_acc4 = nullptr, int nr_on = 0,
+template <class TQ>
+__device__ __forceinline__ void sw_luma4x4_fwd(SwLds &s, const SwArgs &a, const SwQp &Q, TQ tq, int cat, bool dc_out, int lane, int *nr_acc4 = nullptr, int nr_on = 0,
                                                int mask8 = 0xf)
 {
     i16 c[16], lv[16];
@@ -493,9 +630,15 @@ __device__ __forceinline__ void sw_luma4x4_fwd(SwLds &s, const SwArgs &a, const 
         WAVE_SYNC();
 #pragma nounroll
         for (int it = 0; it < 4; it++)
-            if ((mask8 >> it) & 1)
+            if ((mask8 >> it) & 1) {
+            if constexpr (TQ::PSY) {
+                sw_psy_src4(s, tq, 4 * it + (lane >> 4), lane);
+                td_trellis_wave(tq.r->tw, (u32 *)s.patch, &s.coef[4 * it + (lane >> 4)][0], true, s.qmf[cat], tq.r->unq4[cat], tq.r->w4z, tq.r->zz4, tq.r->cabac, dc_out ? 1 : 2,
+                                d_trellis_lambda2[cat == 0][Q.qp], dc_out ? 1 : 0, 0, 16, lane, SW_PSY_FENC(s) + (lane & 48), SwPw4(), tq.psy);
+            } else
             td_trellis_wave(tq.r->tw, (u32 *)s.patch, &s.coef[4 * it + (lane >> 4)][0], true, s.qmf[cat], tq.r->unq4[cat], tq.r->w4z, tq.r->zz4, tq.r->cabac, dc_out ? 1 : 2,
                             d_trellis_lambda2[cat == 0][Q.qp], dc_out ? 1 : 0, 0, 16, lane);
+            }
         WAVE_SYNC();
     }
     if (mine) {
@@ -539,7 +682,8 @@ __device__ __forceinline__ void sw_ll_i8x8(SwLds &s, int idx, int &cbp_luma, int
 __device__ __forceinline__ int sw_ll_luma16(SwLds &s, bool dc_out, int lane);
 __device__ __forceinline__ int sw_ll_chroma(SwLds &s, int lane);
 // x264_macroblock_encode's inter 4x4-transform branch; returns cbp_luma, fills s.nnz[0..15]
-__device__ __forceinline__ int sw_encode_inter_luma(SwLds &s, const SwArgs &a, const SwQp &Q, SwTq tq, int lane, int *nr_acc4 = nullptr, int nr_on = 0)
+template <class TQ>
+__device__ __forceinline__ int sw_encode_inter_luma(SwLds &s, const SwArgs &a, const SwQp &Q, TQ tq, int lane, int *nr_acc4 = nullptr, int nr_on = 0)
 {
     if (a.lossless) return sw_ll_luma16(s, false, lane);
     sw_luma4x4_fwd(s, a, Q, tq, 1, false, lane, nr_acc4, nr_on);
@@ -567,7 +711,8 @@ __device__ __forceinline__ int sw_encode_inter_luma(SwLds &s, const SwArgs &a, c
     return keep;
 }
 // x264_mb_encode_i16x16 (prediction already in s.fd); returns cbp_luma, fills s.nnz[0..15], s.nnz[24]
-__device__ __forceinline__ int sw_encode_i16x16(SwLds &s, const SwArgs &a, const SwQp &Q, SwTq tq, int lane, bool b_slice = false)
+template <class TQ>
+__device__ __forceinline__ int sw_encode_i16x16(SwLds &s, const SwArgs &a, const SwQp &Q, TQ tq, int lane, bool b_slice = false)
 {
     if (a.lossless) return sw_ll_luma16(s, true, lane);
     sw_luma4x4_fwd(s, a, Q, tq, 0, true, lane);
@@ -651,7 +796,8 @@ __device__ __forceinline__ int sw_encode_i16x16(SwLds &s, const SwArgs &a, const
     return keep;
 }
 // x264_mb_encode_8x8_chroma; returns cbp_chroma, fills s.nnz[16..23], s.nnz[25..26]
-__device__ __forceinline__ int sw_encode_chroma(SwLds &s, const SwArgs &a, const SwQp &Q, SwTq tq, int b_inter, int lane)
+template <class TQ>
+__device__ __forceinline__ int sw_encode_chroma(SwLds &s, const SwArgs &a, const SwQp &Q, TQ tq, int b_inter, int lane)
 {
     if (a.lossless) return sw_ll_chroma(s, lane);
     const int cat = 2 + b_inter, b_decimate = b_inter && a.dct_decimate;
@@ -822,7 +968,8 @@ __device__ __forceinline__ int sw_probe_pskip(SwLds &s, const SwRefs &refs, cons
 // for the two 1-D passes (32 lanes), then 64 lanes x one coefficient per block.  Leaves the quantised
 // coefficients (transposed storage) in s.coef[4*b..][..] = [4][64], levels in s.lv_y8, per block
 // s.score[b] = decimate_score64 | nz << 8.  cat: 0 intra, 1 inter.
-__device__ __forceinline__ void sw_luma8x8_fwd(SwLds &s, const SwQp &Q, SwTq tq, int cat, int mask, int lane, int *nr_acc8 = nullptr, int nr_on = 0)
+template <class TQ>
+__device__ __forceinline__ void sw_luma8x8_fwd(SwLds &s, const SwQp &Q, TQ tq, int cat, int mask, int lane, int *nr_acc8 = nullptr, int nr_on = 0)
 {
     i16 *tmp = s.t8, *coef = &s.coef[0][0];
     const int b = lane >> 3, k8 = lane & 7;
@@ -866,8 +1013,14 @@ __device__ __forceinline__ void sw_luma8x8_fwd(SwLds &s, const SwQp &Q, SwTq tq,
     if (tq.on) {                                      // x264_quant_8x8_trellis (R/encoder/rdo.c:652-660): one block at a time (its level lists fill the scratch area), sixteen lanes
 #pragma nounroll
         for (int j = 0; j < 4; j++)
-            if ((mask >> j) & 1)
+            if ((mask >> j) & 1) {
+                if constexpr (TQ::PSY) {
+                    sw_psy_src8(s, tq, j, lane);
+                    td_trellis_wave(tq.r->tw, (u32 *)s.patch, coef + 64 * j, lane < 16, s.q8mf[cat], tq.r->unq8[cat], tq.r->w8z, tq.r->zz8, tq.r->cabac, 5, d_trellis_lambda2[cat == 0][Q.qp], 0, 0, 64, lane,
+                                    SW_PSY_FENC(s), SwPw8(), tq.psy);
+                } else
                 td_trellis_wave(tq.r->tw, (u32 *)s.patch, coef + 64 * j, lane < 16, s.q8mf[cat], tq.r->unq8[cat], tq.r->w8z, tq.r->zz8, tq.r->cabac, 5, d_trellis_lambda2[cat == 0][Q.qp], 0, 0, 64, lane);
+            }
         WAVE_SYNC();
 #pragma unroll
         for (int j = 0; j < 4; j++)
@@ -934,7 +1087,8 @@ __device__ __forceinline__ void sw_luma8x8_add(SwLds &s, int cat, int qp, int ke
     WAVE_SYNC();
 }
 // inter, 8x8 transform (R/encoder/macroblock.c:627-669); returns cbp_luma, fills s.nnz[0..15]
-__device__ __forceinline__ int sw_encode_inter_luma8(SwLds &s, const SwArgs &a, const SwQp &Q, SwTq tq, int lane, int *nr_acc8 = nullptr, int nr_on = 0)
+template <class TQ>
+__device__ __forceinline__ int sw_encode_inter_luma8(SwLds &s, const SwArgs &a, const SwQp &Q, TQ tq, int lane, int *nr_acc8 = nullptr, int nr_on = 0)
 {
     sw_luma8x8_fwd(s, Q, tq, 1, 0xf, lane, nr_acc8, nr_on);
     const int b_decimate = a.dct_decimate && !tq.on;           // "8x8 trellis is inherently optimal decimation", macroblock.c:630
@@ -954,7 +1108,8 @@ __device__ __forceinline__ int sw_encode_inter_luma8(SwLds &s, const SwArgs &a, 
     return cbp;
 }
 // x264_mb_encode_i8x8 for block idx (prediction already in s.fd)
-__device__ __forceinline__ void sw_encode_i8x8(SwLds &s, const SwArgs &a, const SwQp &Q, SwTq tq, int idx, int &cbp_luma, int lane)
+template <class TQ>
+__device__ __forceinline__ void sw_encode_i8x8(SwLds &s, const SwArgs &a, const SwQp &Q, TQ tq, int idx, int &cbp_luma, int lane)
 {
     if (a.lossless) { sw_ll_i8x8(s, idx, cbp_luma, lane); return; }
     sw_luma8x8_fwd(s, Q, tq, 0, 1 << idx, lane);
@@ -987,7 +1142,8 @@ __device__ __forceinline__ int sw_inv4_quad(int v, int k, int last)   // dct.c:1
     const int r = k == 0 ? e + g : k == 1 ? f + h : k == 2 ? f - h : e - g;
     return (int)(i16)(last ? (r + 32) >> 6 : r);
 }
-__device__ __forceinline__ void sw_encode_i4x4(SwLds &s, const SwArgs &a, const SwQp &Q, SwTq tq, int idx, int &cbp_luma, int lane)
+template <class TQ>
+__device__ __forceinline__ void sw_encode_i4x4(SwLds &s, const SwArgs &a, const SwQp &Q, TQ tq, int idx, int &cbp_luma, int lane)
 {
     if (a.lossless) { sw_ll_i4x4(s, idx, cbp_luma, lane); return; }
     int bx, by;
@@ -1001,6 +1157,11 @@ __device__ __forceinline__ void sw_encode_i4x4(SwLds &s, const SwArgs &a, const 
     if (tq.on) {                                      // x264_quant_4x4_trellis( .., DCT_LUMA_4x4, 1, idx ), macroblock.c:134
         if (lane < 16) s.coef[idx][l16] = (i16)v;
         WAVE_SYNC();
+        if constexpr (TQ::PSY) {
+            sw_psy_src4(s, tq, idx, lane);
+            td_trellis_wave(tq.r->tw, (u32 *)s.patch, &s.coef[idx][0], lane < 16, s.qmf[0], tq.r->unq4[0], tq.r->w4z, tq.r->zz4, tq.r->cabac, 2, d_trellis_lambda2[1][Q.qp], 0, 0, 16, lane,
+                            SW_PSY_FENC(s), SwPw4(), tq.psy);
+        } else
         td_trellis_wave(tq.r->tw, (u32 *)s.patch, &s.coef[idx][0], lane < 16, s.qmf[0], tq.r->unq4[0], tq.r->w4z, tq.r->zz4, tq.r->cabac, 2, d_trellis_lambda2[1][Q.qp], 0, 0, 16, lane);
         WAVE_SYNC();
         q = s.coef[idx][l16];
@@ -1309,6 +1470,7 @@ struct SwDesc { SwArgs a; SwRefs t; SwRd r; };
 template <int WPE, bool LL = false, bool RD = false, bool BS = false, bool TD = false, bool RF = false, bool CH = false>       // TD: the extended B kernel (temporal direct prediction, lookahead candidates)
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE))) void k_slice_sweep(SwArgs a, SwRefs refs_k, SwRd rd_k, const SwDesc *tab)
 {
+    constexpr bool PT = false;
 #include "slice_sweep_body.h"
 }
 
@@ -1319,9 +1481,28 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE))) void 
 template <bool RF, bool CH>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(RF ? 1 : 2))) void k_lossless_raster(SwArgs a, SwRefs refs_k, SwRd rd_k, const SwDesc *tab)
 {
-    constexpr bool LL = true, RD = true, BS = false, TD = false;
+    constexpr bool LL = true, RD = true, BS = false, TD = false, PT = false;
 #include "slice_sweep_body.h"
 }
+
+// The lossy raster variant with psy-trellis (--psy-rd A:B with B > 0 under --trellis 1 or 2; PT, a compile-time constant that is false in the two
+// templates above): the trellis quantiser's price of a luma coefficient gains rdo.c:555-562's term.  Kernels of their own name over the same body, like the
+// lossless ones and for the same reason.  One B kernel, the extended one (TD): a lock-step B launch with psy-trellis goes there as a table's
+// does.  All of them are allowed a whole SIMD's register file (one wave per SIMD where they take it) instead of scratch memory: held to 256 registers
+// the chain-table I / P body and the B bodies spilled 4 to 47 registers with the psy code in them, and a kernel of this name may not spill.
+template <bool BS, bool TD, bool RF, bool CH>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1))) void k_psy_raster(SwArgs a, SwRefs refs_k, SwRd rd_k, const SwDesc *tab)
+{
+    constexpr bool LL = false, RD = true, PT = true;
+#include "slice_sweep_body.h"
+}
+// its launch functions (frame_slice_psy_*.hip), called by the launch functions of the kinds below when SwRd::psy_trellis is set; a chain-table
+// launch function sees only the device's table, so x264hip_slice_sweep_chains says which by sw_table_psy around its launches
+typedef void SwLaunchPsy(const SwArgs &a, const SwRefs &t, const SwRd &r, hipStream_t stream);
+typedef void SwLaunchPsyChains(const struct SwDesc *tab, int n, hipStream_t stream);
+SwLaunchPsy x264hip_launch_psy_rd, x264hip_launch_psy_rf, x264hip_launch_psy_bt;
+SwLaunchPsyChains x264hip_launch_psy_rd_ch, x264hip_launch_psy_rf_ch, x264hip_launch_psy_bt_ch;
+extern thread_local bool sw_table_psy;
 
 // the launch functions of the instantiation files (frame_slice_*.hip) and the table of kinds the host side walks
 #include "sweep_tables.h"

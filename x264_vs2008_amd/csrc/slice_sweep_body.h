@@ -1,6 +1,6 @@
 // slice_sweep_body.h -- the body of the macroblock sweep, textually included by the kernel templates at the end of slice_kernel.h
-// (k_slice_sweep and k_lossless_raster).  In scope: the kernel's parameters (SwArgs a, SwRefs refs_k, SwRd rd_k, const SwDesc *tab) and the
-// compile-time constants LL, RD, BS, TD, RF, CH described there.
+// (k_slice_sweep, k_lossless_raster and k_psy_raster).  In scope: the kernel's parameters (SwArgs a, SwRefs refs_k, SwRd rd_k, const SwDesc *tab) and the
+// compile-time constants LL, RD, BS, TD, RF, CH, PT described there.
     static_assert(!CH || RD, "the chain table belongs to the raster variant");
     SwRd rd_l;
     if constexpr (CH) {
@@ -248,7 +248,11 @@
         int stat_intra = 0, stat_inter = 0, analysed = 0;
         // x264_mb_analyse_init (R/encoder/analyse.c:235-252): h->mb.b_trellis while analysing, i_skip_intra
         const int mbrd = RD ? rd.mbrd : 0;
-        SwTq tq = {RD && rd.trellis > 1 && mbrd, &sr};
+        typename std::conditional<PT, SwTqPsy, SwTq>::type tq = {RD && rd.trellis > 1 && mbrd, &sr};
+        // psy-trellis, --trellis 2: with the RD levels both source transforms are the macroblock's own from its first trial on (x264_mb_cache_fenc_satd);
+        // below them nobody writes the arrays -- zeros, except in a B slice at subme 6, whose I and P slices ARE at the RD levels: it reads what the last
+        // macroblock they analysed left.  --trellis 1: sw_psy_after_analysis, once the analysis is over.
+        if constexpr (PT) sw_tq_set_psy(tq, rd.psy_trellis, rd.trellis > 1 && !mbrd ? (BS ? SW_PSY_KEPT : SW_PSY_ZERO) : SW_PSY_OWN, sw_psy_carry(rd, bz));
         int skip_intra = a.lossless ? 0 : mbrd ? 2 : (RD ? (!rd.trellis && !a.nr) : 1);
         (void)skip_intra;
 
@@ -457,12 +461,16 @@
                 WAVE_SYNC();
             }
         };
+        auto psy_after_analysis = [&]() {   // analyse.c:2770-2771, with t8 = h->mb.b_transform_8x8 as the analysis left it
+            if constexpr (PT) { if (rd.trellis == 1) sw_psy_after_analysis(s, tq, t8, lane); }
+        };
         auto encode_mb = [&](int final_pass) {
             if (type == T_P_SKIP) { encode_pskip(); return; }
             cbp_luma = 0; cbp_chroma = 0;
             if (lane < 32) s.nnz[lane] = 0;
             WAVE_SYNC();
             if (BS && type == T_B_SKIP) return;              // x264_macroblock_encode_skip: the prediction (made by the caller) is the reconstruction
+            if (final_pass && IS_INTRA_T(type)) psy_after_analysis();
             if (type == T_I_16x16) {
                 t8 = 0;
                 analyse_chroma();
@@ -537,6 +545,7 @@
                     const int c4 = sw_cmp_luma16(s, 1, lane);
                     t8 = c8 < c4;
                 }
+                if (final_pass) psy_after_analysis();
                 const int nr_on = a.nr && final_pass;        // h->mb.b_noise_reduction is off while analysing (analyse.c:237,2769)
                 if (nr_on) { if (t8) nr_n8 += 4; else nr_n4 += 16; }
                 if (LL && t8) {      // zigzag sub_8x8 of the four blocks (macroblock.c:604-615): only x264_mb_analyse_transform_rd turns the 8x8 transform on here
@@ -552,6 +561,8 @@
         // ---- the RD levels: x264_mb_cache_fenc_satd, ssd_mb, x264_macroblock_size_cabac, x264_rd_cost_mb ----
         int fenc_satd_sum = 0, fenc_sa8d_sum = 0;
         auto cache_fenc_satd = [&]() {     // R/encoder/analyse.c:509-537 (the 16x16 sums; sub-partition RD is not built)
+            // :515-516.  Only a B slice below the RD levels ever reads what this leaves (above): subme 6, whose I and P slices run this
+            if constexpr (PT && !BS) { if (rd.trellis == 2 && a.subme == 6) sw_psy_before_trials(s, tq, a.transform8x8, lane); }
             if (!rd.psy_rd) return;
             int v4 = 0, v8 = 0;
             if (lane < 16) {
@@ -1215,6 +1226,7 @@
                             const int t8_bak = t8;
                             PROF(6);
                             if (!(fin && type == T_I_PCM)) encode_mb(fin ? 1 : 0);
+                            else psy_after_analysis();               // I_PCM is not a skip: the arrays are refreshed, nothing is quantised
                             if (fin) { encoded = true; break; }
                             PROF(0);
                             // distortion, and the syntax priced against a copy of the live contexts.  Like the reference this leaves `type`

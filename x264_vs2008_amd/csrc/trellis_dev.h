@@ -27,8 +27,11 @@ static __device__ const int d_trellis_lambda2[2][52] = {        // lambda2_tab, 
 // h->unquant4_mf[cat][qp]) in raster order; weight: x264_dct4/8_weight2_zigzag (scan order; unused for DC); zz: scan position ->
 // raster index; st: the 460 context states (read only); cat: block category as in cabac_dev.h; dc: DC block (one multiplier);
 // b_ac: scan position 0 is not part of the block.  Returns "some level is not zero".
-template <class TS, class DCT, class MF, class UNQ, class WT, class ZZ, class ST>
-CD_FN int td_trellis_quant(TS &t, DCT dct, MF mf, UNQ unq, WT weight, ZZ zz, ST st, int cat, int lambda2, int b_ac, int dc, int n_coef)
+// PSY (psy-trellis, rdo.c:555-562): fenc holds the source block's own transform in scan order (h->mb.pic.fenc_dct4 / fenc_dct8 [idx]),
+// psy_w is x264_dct4 / dct8_weight_tab by raster index, psy is h->mb.i_psy_trellis.  A compile-time flag: without it nothing of the
+// three is touched and the function is the one it was.
+template <bool PSY, class TS, class DCT, class MF, class UNQ, class WT, class ZZ, class ST, class FE, class PW>
+CD_FN int td_trellis_quant_t(TS &t, DCT dct, MF mf, UNQ unq, WT weight, ZZ zz, ST st, int cat, int lambda2, int b_ac, int dc, int n_coef, FE fenc, PW psy_w, int psy)
 {
     const int f = 1 << 15;
     int i, j, n_lvl = 1, cur = 0;
@@ -73,7 +76,13 @@ CD_FN int td_trellis_quant(TS &t, DCT dct, MF mf, UNQ unq, WT weight, ZZ zz, ST 
 #pragma nounroll
         for (int lvl = q; lvl >= q - 1; lvl--) {
             const int unq_lvl = ((dc ? (int)unq[0] << 1 : (int)unq[zz[i]]) * lvl + 128) >> 8, d = coef - unq_lvl;
-            const long long ssd = (long long)d * d * (dc ? 256 : (int)weight[i]);
+            long long ssd = (long long)d * d * (dc ? 256 : (int)weight[i]);
+            if constexpr (PSY) {
+                if (psy && i && !dc && cat != 4) {
+                    const int sign = (neg >> i) & 1 ? -1 : 1, predicted = (int)fenc[i] - coef * sign;
+                    ssd -= (int)psy_w[zz[i]] * (psy * cd_abs(predicted + unq_lvl * sign));
+                }
+            }
 #pragma nounroll
             for (j = 0; j < 8; j++) {
                 if (t.nodes[prv][j].score == TD_INF) continue;
@@ -120,4 +129,14 @@ CD_FN int td_trellis_quant(TS &t, DCT dct, MF mf, UNQ unq, WT weight, ZZ zz, ST 
         j = t.lvl_next[j];
     }
     return nz != 0;
+}
+template <class TS, class DCT, class MF, class UNQ, class WT, class ZZ, class ST>
+CD_FN int td_trellis_quant(TS &t, DCT dct, MF mf, UNQ unq, WT weight, ZZ zz, ST st, int cat, int lambda2, int b_ac, int dc, int n_coef)
+{
+    return td_trellis_quant_t<false>(t, dct, mf, unq, weight, zz, st, cat, lambda2, b_ac, dc, n_coef, 0, 0, 0);
+}
+template <class TS, class DCT, class MF, class UNQ, class WT, class ZZ, class ST, class FE, class PW>
+CD_FN int td_trellis_quant(TS &t, DCT dct, MF mf, UNQ unq, WT weight, ZZ zz, ST st, int cat, int lambda2, int b_ac, int dc, int n_coef, FE fenc, PW psy_w, int psy)
+{
+    return td_trellis_quant_t<true>(t, dct, mf, unq, weight, zz, st, cat, lambda2, b_ac, dc, n_coef, fenc, psy_w, psy);
 }

@@ -262,9 +262,11 @@ def encode_streams(lib, p, sources, n_frames, sinks, psnr=0, ssim=0, verbose=Fal
     common = dict(qp=p.qp_constant, me_method=p.me_method, me_range=p.me_range, subme=p.subpel_refine, n_refs=p.frame_reference, inter=p.inter, intra=p.intra,
                   transform8x8=p.transform_8x8, fast_pskip=p.fast_pskip, dct_decimate=p.dct_decimate, chroma_me=p.chroma_me, cabac=p.cabac, deblock=p.deblocking_filter,
                   alpha_c0=p.deblocking_filter_alphac0, beta=p.deblocking_filter_beta, keyint=p.keyint_max, mixed_refs=p.mixed_references, noise_reduction=p.noise_reduction,
-                  mv_range=p.mv_range, trellis=p.trellis, psy_rd=p.psy_rd, aq_mode=p.aq_mode, aq_strength=p.aq_strength, qp_min=p.qp_min, qp_max=p.qp_max)
-    # chroma_qp_offset: the encoders apply the psy shift themselves (as x264_validate_parameters did to p): hand them the value before it
+                  mv_range=p.mv_range, trellis=p.trellis, psy_rd=p.psy_rd, psy_trellis=p.psy_trellis, aq_mode=p.aq_mode, aq_strength=p.aq_strength, qp_min=p.qp_min, qp_max=p.qp_max)
+    # chroma_qp_offset: the encoders apply the two psy shifts themselves (as x264_validate_parameters did to p): hand them the value before both
     shift = (1 if p.psy_rd < 0.25 else 2) if p.d_psy_rd_fix8 else 0
+    if sl.psy_trellis_fix8(p.psy_trellis):     # h->mb.i_psy_trellis (p.psy_trellis is 0 without trellis)
+        shift += 1 if p.psy_trellis < 0.25 else 2
     common["chroma_qp_offset"] = p.chroma_qp_offset + shift
     coded = 0
     if not needs_lookahead(p):

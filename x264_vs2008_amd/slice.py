@@ -52,6 +52,28 @@ def iframe_qp(qp, ip_factor=1.4):
     return min(max(int(qp - 6.0 * math.log(float(np.float32(ip_factor))) / math.log(2.0) + 0.5), 0), 51)
 
 
+def rd_side_options(cabac, subme, trellis, psy_rd, psy_trellis, chroma_qp_offset):
+    """x264_validate_parameters (R/encoder/encoder.c:493-522): what the RD-side options do to each other.  Returns (i_trellis, h->mb.i_psy_rd,
+    h->mb.i_psy_trellis, i_chroma_qp_offset).  Host arithmetic only."""
+    trellis = min(max(trellis, 0), 2) if cabac else 0
+    psy_rd = 0.0 if subme < 6 else min(max(float(psy_rd), 0.0), 10.0)
+    psy_rd_fix = int(np.float32(psy_rd) * 256 + 0.5)                  # FIX8
+    # psy-trellis (--psy-rd A:B's B, :502-505,515): off without trellis, FIX8 of a quarter of the strength -- in the reference's float
+    psy_trellis = min(max(float(psy_trellis), 0.0), 10.0) if trellis else 0.0
+    psy_trellis_fix = psy_trellis_fix8(psy_trellis)
+    # each lowers the chroma QP offset (:509-518); one clip after both (:521)
+    if psy_rd_fix:
+        chroma_qp_offset -= 1 if psy_rd < 0.25 else 2
+    if psy_trellis_fix:
+        chroma_qp_offset -= 1 if np.float32(psy_trellis) < 0.25 else 2
+    return trellis, psy_rd_fix, psy_trellis_fix, min(max(chroma_qp_offset, -12), 12)
+
+
+def psy_trellis_fix8(psy_trellis):
+    """h->mb.i_psy_trellis of a VALIDATED strength (0 without trellis already): FIX8 of a quarter of it, in the reference's float."""
+    return int(float(np.float32(psy_trellis) / np.float32(4) * np.float32(256)) + 0.5)
+
+
 class DeviceState:
     """One x264hip_mb_state: allocated by the library, read back as numpy arrays [batch][n][...]."""
 
@@ -81,7 +103,7 @@ class ChainEncoder:
                  transform8x8=0, fast_pskip=1, dct_decimate=1, chroma_me=1, cabac=0, deblock=0, alpha_c0=0, beta=0,
                  chroma_qp_offset=0, keyint=0, mixed_refs=0, noise_reduction=0, mv_range=0,
                  trellis=0, psy_rd=0.0, aq_mode=0, aq_strength=1.0, write=0, cabac_init_idc=0, qp_min=0, qp_max=51, payload_cap=0, raster=None,
-                 bframes=0, weightb=0, direct_pred=1, lanes=0, levels=True, psnr=0, ssim=0, mb_stats=0):
+                 bframes=0, weightb=0, direct_pred=1, lanes=0, levels=True, psnr=0, ssim=0, mb_stats=0, psy_trellis=0.0):
         self.lib = lib
         self.lossless = int(qp == 0)
         # param.analyse.b_psnr / b_ssim: the quality pass (quality.py) behind every frame -- a B frame's behind its sweep, on its unfiltered
@@ -95,12 +117,7 @@ class ChainEncoder:
             transform8x8 = int(bool(transform8x8 and cabac))
             if not transform8x8:
                 inter, intra = inter & ~2, intra & ~2
-        # x264_validate_parameters (R/encoder/encoder.c:493-522): what the RD-side options do to each other
-        trellis = min(max(trellis, 0), 2) if cabac else 0
-        psy_rd = 0.0 if subme < 6 else min(max(float(psy_rd), 0.0), 10.0)
-        self.psy_rd_fix = int(np.float32(psy_rd) * 256 + 0.5)             # FIX8
-        if self.psy_rd_fix:
-            chroma_qp_offset = min(max(chroma_qp_offset - (1 if psy_rd < 0.25 else 2), -12), 12)
+        trellis, self.psy_rd_fix, self.psy_trellis_fix, chroma_qp_offset = rd_side_options(cabac, subme, trellis, psy_rd, psy_trellis, chroma_qp_offset)
         aq_strength = min(max(float(aq_strength), 0.0), 3.0)
         aq_mode = 0 if aq_strength == 0 else min(max(aq_mode, 0), 1)
         # the raster-order variant of the sweep: needed by the RD levels, trellis, adaptive quantisation, or simply to get the payload
@@ -144,6 +161,9 @@ class ChainEncoder:
             # fails); one record per chain, zero like the reference's freshly allocated x264_t.  Per chain, and a chain's frames stay in
             # order, so temporal direct prediction also goes with the encoder that lets the chains drift apart (AsyncStreamEncoder)
             rb["stale"] = DeviceArray(lib, (B, 8), np.int16)
+            # x264hip_slice_rd.psy_carry: h->mb.pic.fenc_dct4 | fenc_dct8, which the reference never clears either; zero like its x264_t
+            if self.psy_trellis_fix:
+                rb["psy_carry"] = DeviceArray(lib, (B, 512), np.int16)
             self.rd_bufs = rb
             self.payload_cap = cap
         if self.cavlc and not levels:
@@ -179,6 +199,8 @@ class ChainEncoder:
                 raise ValueError("lanes: B frames run in the raster variant")
             if direct_pred == 2:
                 raise ValueError("lanes: temporal direct prediction chains every frame to the one coded before it (x264hip_slice_rd.stale)")
+            if self.psy_trellis_fix:
+                raise ValueError("lanes: psy-trellis chains every frame to the one coded before it (x264hip_slice_rd.psy_carry)")
             d = self.ctx.dims
             for _ in range(lanes):
                 lc = FrameCtx(lib, width, height, batch=batch)
@@ -256,7 +278,8 @@ class ChainEncoder:
                        qp_min=ro["qp_min"], qp_max=ro["qp_max"], f_qpm=f_qpm, aq_offset=aq_offset,
                        cost_mv_all=rb["cost_mv_all"].ptr, unquant4_mf=rb["unquant4_mf"].ptr, unquant8_mf=rb["unquant8_mf"].ptr,
                        payload=rb["payload"].ptr, payload_cap=self.payload_cap, payload_len=rb["payload_len"].ptr, mb_bits=rb["mb_bits"].ptr,
-                       stale=rb["stale"].ptr, i_frame_stride=i_frame_stride)
+                       stale=rb["stale"].ptr, i_frame_stride=i_frame_stride, psy_trellis=self.psy_trellis_fix,
+                       psy_carry=rb["psy_carry"].ptr if "psy_carry" in rb else None)
 
     def filter_kept(self, c, recon, s):
         """x264_fdec_filter_row for a whole kept frame, enqueued on context c: loop filter (from the x264hip_mb_state s), borders, half-pel
