@@ -81,6 +81,29 @@ typedef struct {
 } x264hip_cavlc_params;
 int x264hip_cavlc_write_frame(x264hip_frame_ctx *c, const x264hip_mb_state *st, const x264hip_cavlc_params *p);
 
+/* The CABAC writer as a pass: x264_macroblock_write_cabac with x264_slice_write's terminal bins and skip flags (R/encoder/cabac.c:32-1022,
+ * R/encoder/encoder.c:1192-1273) for every chain's I or P slice, from the state x264hip_slice_sweep_frame left.  Below the RD levels the
+ * analysis never reads the CABAC contexts, so a CABAC slice there needs no writer in the macroblock loop: the wavefront variant codes it at
+ * constant QP, the raster variant without its writer (cabac = 1, rd.write = 0) under adaptive quantisation, and this call writes the bytes
+ * the in-loop writer would have.  The state is allocated WITH level arrays.  payload, payload_len, mb_bits: as x264hip_slice_rd's -- device
+ * [batch][payload_cap] bytes with chain b's slice_data() X264HIP_PAYLOAD_LEAD bytes into its slot, [batch] lengths, and (optional)
+ * [batch][n_mb] bit positions after every macroblock.  cabac_init_idc, i_frame, i_frame_stride: as x264hip_slice_rd's (chain b's flush takes
+ * i_frame + b * i_frame_stride).  Asynchronous on the context's stream.  The pass stops before a macroblock whose worst case (8192 bytes,
+ * the in-loop writer's bound) might not fit the slot, and at an I_PCM macroblock (none occurs below the RD levels): x264hip_slice_sweep_status
+ * then reports an abort, and nothing is written past the slot.  B slices, states without level arrays, frames of more than 512 macroblocks
+ * per row and payload slots below 8192 + 128 bytes are refused. */
+typedef struct {
+    int slice_type;            /* 0 P, 2 I */
+    int n_ref0;                /* h->mb.pic.i_fref[0] */
+    int analyse_inter;         /* param.analyse.inter (kept beside x264hip_cavlc_params; CABAC always codes the sub-partition types) */
+    int transform8x8;          /* pps->b_transform_8x8_mode */
+    int slice_qp;              /* h->sh.i_qp: the contexts' initial states and the first mb_qp_delta's base */
+    int cabac_init_idc;
+    int i_frame, i_frame_stride;
+    uint8_t *payload; int payload_cap; int32_t *payload_len; int32_t *mb_bits;
+} x264hip_cabac_params;
+int x264hip_cabac_write_frame(x264hip_frame_ctx *c, const x264hip_mb_state *st, const x264hip_cabac_params *p);
+
 /* The writer for chains that do not move in lock step: the counterpart of x264hip_slice_sweep_chains for an all-CAVLC chain table (every
  * entry of the sweep's table with cabac = 0 and rd.write = 0).  Every entry is ONE chain's slice: the chain (batch element), the state its
  * sweep wrote (that chain's copy of the x264hip_mb_state) and the slice's x264hip_cavlc_params -- slice type, n_ref0, slice QP and the

@@ -153,6 +153,13 @@ class CavlcParams(C.Structure):
                 ("payload", C.c_void_p), ("payload_cap", C.c_int), ("payload_len", C.c_void_p), ("mb_bits", C.c_void_p), ("slice_qp", C.c_int)]
 
 
+class CabacParams(C.Structure):
+    """One frame's slices for x264hip_cabac_write_frame: the CABAC writer as a pass behind the sweep."""
+    _fields_ = [("slice_type", C.c_int), ("n_ref0", C.c_int), ("analyse_inter", C.c_int), ("transform8x8", C.c_int), ("slice_qp", C.c_int),
+                ("cabac_init_idc", C.c_int), ("i_frame", C.c_int), ("i_frame_stride", C.c_int),
+                ("payload", C.c_void_p), ("payload_cap", C.c_int), ("payload_len", C.c_void_p), ("mb_bits", C.c_void_p)]
+
+
 class ChainCavlc(C.Structure):
     """One chain's slice in a launch of x264hip_cavlc_write_chains."""
     _fields_ = [("chain", C.c_int), ("state", C.c_void_p), ("params", C.c_void_p)]
@@ -207,7 +214,8 @@ RECORDS = {"x264hip_cfg": Cfg, "x264hip_frame_dims": Dims, "x264hip_picture": Pi
            "x264hip_slice_params": SliceParams, "x264hip_slice_b": SliceB, "x264hip_nr_state": NrState, "x264hip_residual_params": ResidualParams,
            "x264hip_deblock_params": DeblockParams, "x264hip_lookahead_params": LookaheadParams, "x264hip_look_need": Need,
            "x264hip_look_frame": Frame, "x264hip_look_slot": LookSlot, "x264hip_look_task": LookTask, "x264hip_look_params": LookParams,
-           "x264hip_chain_sweep": ChainSweep, "x264hip_cavlc_params": CavlcParams, "x264hip_chain_cavlc": ChainCavlc,
+           "x264hip_chain_sweep": ChainSweep, "x264hip_cavlc_params": CavlcParams, "x264hip_cabac_params": CabacParams,
+           "x264hip_chain_cavlc": ChainCavlc,
            "x264hip_encoder_params": EncoderParams, "x264hip_slice_header": SliceHeader, "x264hip_frame_report": FrameReport,
            "x264hip_chain_report": ChainReport, "x264hip_stat_frame": StatFrame}
 
@@ -317,6 +325,7 @@ PROTOTYPES = {
     "x264hip_frame_ctx_set_b_stream": "i:pp",
     "x264hip_frame_ctx_elements": "i:ppi",
     "x264hip_cavlc_write_frame": "i:ppp",
+    "x264hip_cabac_write_frame": "i:ppp",
     "x264hip_cavlc_write_chains": "i:ppipp",
     "x264hip_chain_cavlc_bytes": "z:",
     # include/x264hip_stream.h

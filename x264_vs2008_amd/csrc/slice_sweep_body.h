@@ -1325,9 +1325,10 @@
                     return;
                 }
                 if (!IS_SKIP_T(type)) mb_qp = UNI(sr.tmp_i[1]);
-            } else if (!a.cabac && type == T_I_16x16 && !(cbp_luma | cbp_chroma) && !UNI((int)s.nnz[24])) {
-                // a CAVLC slice is written after the sweep (x264hip_cavlc_write_frame), but cavlc_qp_delta's side effect belongs here: an I_16x16
-                // macroblock without any coefficient takes the previous QP (R/encoder/cavlc.c:205-211), which the next macroblock's QP rule reads
+            } else if (type == T_I_16x16 && !(cbp_luma | cbp_chroma) && !UNI((int)s.nnz[24])) {
+                // a slice without the writer in the loop is written after the sweep (x264hip_cavlc_write_frame, x264hip_cabac_write_frame), but the
+                // side effect of either writer's mb_qp_delta belongs here: an I_16x16 macroblock without any coefficient takes the previous QP
+                // (R/encoder/cavlc.c:205-211, R/encoder/cabac.c:270-276), which the next macroblock's QP rule and the loop filter read
                 mb_qp = last_qp;
             }
             // x264_macroblock_cache_save's QP rules (R/common/macroblock.c:1244-1272): a macroblock without coefficients has no QP of its own

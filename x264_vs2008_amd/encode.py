@@ -230,11 +230,15 @@ def check_built(p):
                          "(--subme 5 and below are)" % p.subpel_refine)
 
 
-def encode_streams(lib, p, sources, n_frames, sinks, psnr=0, ssim=0, verbose=False, stats=None, observe=None):
+def encode_streams(lib, p, sources, n_frames, sinks, psnr=0, ssim=0, verbose=False, stats=None, observe=None, cabac_pass=None):
     """p: validated parameters (mux.encoder_params); sources: readers of equal picture size; sinks: binary files, one per source.
     psnr / ssim: measure every coded frame (x264hip_frame_report_*); stats: a list that receives one quality.Stat per stream (the caller prints
     its summary and closes it); verbose: x264_encoder_frame_end's line per frame on stderr; observe(enc, chain, frame, slice type, picture, state,
-    muxer): called for every accounted frame while its reconstruction and state are still on the device (a checker's view of what was measured)."""
+    muxer): called for every accounted frame while its reconstruction and state are still on the device (a checker's view of what was measured).
+    cabac_pass: who writes a CABAC slice of a stream without lookahead (constant QP, no B frames, no scene cuts) -- None: the pass behind the
+    sweep (ChainEncoder(cabac_pass=True)) below the RD levels, without trellis and adaptive quantisation, not lossless -- where the sweep in
+    front of it is the macroblock-parallel one, measured faster; under --aq-mode 1 both choices code a frame on one wavefront
+    per chain and nothing has been measured, so the in-loop writer stays; True / False force it either way.  The bytes are the same."""
     check_built(p)
     from .quality import Stat
     if stats is not None:
@@ -271,7 +275,9 @@ def encode_streams(lib, p, sources, n_frames, sinks, psnr=0, ssim=0, verbose=Fal
     coded = 0
     if not needs_lookahead(p):
         # x264_slicetype_decide has nothing to decide: an IDR every keyint frames, P frames between, constant QP
-        enc = sl.ChainEncoder(lib, w, h, cq, batch=B, write=1, **common, **measure)
+        if cabac_pass is None:
+            cabac_pass = bool(p.cabac and p.subpel_refine < 6 and not p.trellis and not p.aq_mode and p.qp_constant != 0)
+        enc = sl.ChainEncoder(lib, w, h, cq, batch=B, write=1, cabac_pass=cabac_pass or None, **common, **measure)
         try:
             for t in range(n_frames):
                 for b, s in enumerate(sources):

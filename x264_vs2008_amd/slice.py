@@ -10,7 +10,7 @@ import math
 
 import numpy as np
 
-from .abi import STATE_FIELDS, CavlcParams, ChainCavlc, DeblockParams, MbState, NrState, SliceB, SliceParams, SliceRd
+from .abi import STATE_FIELDS, CabacParams, CavlcParams, ChainCavlc, DeblockParams, MbState, NrState, SliceB, SliceParams, SliceRd
 from . import quality
 from .frame import LAMBDA_TAB, CqmDevice, DeviceArray, FrameCtx
 
@@ -103,7 +103,7 @@ class ChainEncoder:
                  transform8x8=0, fast_pskip=1, dct_decimate=1, chroma_me=1, cabac=0, deblock=0, alpha_c0=0, beta=0,
                  chroma_qp_offset=0, keyint=0, mixed_refs=0, noise_reduction=0, mv_range=0,
                  trellis=0, psy_rd=0.0, aq_mode=0, aq_strength=1.0, write=0, cabac_init_idc=0, qp_min=0, qp_max=51, payload_cap=0, raster=None,
-                 bframes=0, weightb=0, direct_pred=1, lanes=0, levels=True, psnr=0, ssim=0, mb_stats=0, psy_trellis=0.0):
+                 bframes=0, weightb=0, direct_pred=1, lanes=0, levels=True, psnr=0, ssim=0, mb_stats=0, psy_trellis=0.0, cabac_pass=None):
         self.lib = lib
         self.lossless = int(qp == 0)
         # param.analyse.b_psnr / b_ssim: the quality pass (quality.py) behind every frame -- a B frame's behind its sweep, on its unfiltered
@@ -126,8 +126,19 @@ class ChainEncoder:
         # quantisation, and with B frames, which only the raster variant codes: the raster variant without its writer, whose QP rules leave
         # every macroblock's final QP in the state)
         self.cavlc = bool(write and not cabac and subme < 6 and not trellis)
-        self.raster = bool(subme >= 6 or trellis or aq_mode or (write and not self.cavlc) or (self.cavlc and bframes)) if raster is None else bool(raster)
-        self.rd_opt = dict(trellis=trellis, aq_mode=aq_mode, aq_strength=aq_strength, write=int(bool((write and not self.cavlc) or subme >= 6 or trellis)),
+        # cabac_pass: a CABAC slice below the RD levels is written the same way (x264hip_cabac_write_frame): the analysis there never reads the
+        # contexts, so the wavefront variant codes it at constant QP and the raster variant without its writer under adaptive quantisation.
+        # None keeps the in-loop writer and the selection as it was; True asks for the pass and refuses what it does not go with
+        self.cabac_pass = bool(cabac_pass)
+        if self.cabac_pass:
+            why = ("cabac=0" if not cabac else "write=0" if not write else "subme >= 6 (the RD levels price against the live contexts)" if subme >= 6 else
+                   "trellis" if trellis else "bframes (B slices keep the in-loop writer)" if bframes else "lossless" if self.lossless else
+                   "levels=False (the pass reads the coefficient levels)" if not levels else "lanes" if lanes else None)
+            if why:
+                raise ValueError("cabac_pass=True does not go with %s" % why)
+        in_loop = bool(write and not self.cavlc and not self.cabac_pass)
+        self.raster = bool(subme >= 6 or trellis or aq_mode or in_loop or (self.cavlc and bframes)) if raster is None else bool(raster)
+        self.rd_opt = dict(trellis=trellis, aq_mode=aq_mode, aq_strength=aq_strength, write=int(bool(in_loop or subme >= 6 or trellis)),
                            cabac_init_idc=cabac_init_idc, qp_min=qp_min, qp_max=qp_max)
         self.ctx = FrameCtx(lib, width, height, batch=batch)
         self.opt = dict(qp=qp, me_method=me_method, me_range=me_range, subme=subme, n_refs=n_refs, inter=inter, intra=intra,
@@ -168,7 +179,7 @@ class ChainEncoder:
             self.payload_cap = cap
         if self.cavlc and not levels:
             raise ValueError("CAVLC payloads are written from the coefficient levels: levels=False does not go with cabac=0, write=1")
-        if self.cavlc and not self.raster:
+        if (self.cavlc or self.cabac_pass) and not self.raster:
             d = self.ctx.dims
             n = d.mb_w * d.mb_h
             self.payload_cap = payload_cap or (n * MB_BYTES_AVG + MB_BYTES_MAX + 128 + PAYLOAD_LEAD)
@@ -363,6 +374,13 @@ class ChainEncoder:
                              payload=rb["payload"].ptr, payload_cap=self.payload_cap, payload_len=rb["payload_len"].ptr, mb_bits=rb["mb_bits"].ptr,
                              slice_qp=qp)
             c.check(L.x264hip_cavlc_write_frame(c.h, C.byref(state.st), C.byref(cp)), "cavlc_write_frame")
+            self.last_bufs = rb
+        if self.cabac_pass:                            # x264_macroblock_write_cabac for every macroblock of every chain, from the state just written
+            rb = self.last_bufs if self.raster else self.rd_bufs
+            bp = CabacParams(slice_type=stype, n_ref0=len(refs), analyse_inter=o["inter"], transform8x8=o["transform8x8"], slice_qp=qp,
+                             cabac_init_idc=self.rd_opt["cabac_init_idc"], i_frame=self.i_frame, i_frame_stride=self.i_frame_stride,
+                             payload=rb["payload"].ptr, payload_cap=self.payload_cap, payload_len=rb["payload_len"].ptr, mb_bits=rb["mb_bits"].ptr)
+            c.check(L.x264hip_cabac_write_frame(c.h, C.byref(state.st), C.byref(bp)), "cabac_write_frame")
             self.last_bufs = rb
         if self.nr:                            # x264_noise_reduction_update at the end of every frame (R/encoder/encoder.c:1755)
             c.check(L.x264hip_noise_reduction_update(c.h, C.byref(self.nr), o["noise_reduction"]), "noise_reduction_update")
