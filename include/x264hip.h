@@ -396,8 +396,21 @@ typedef struct x264hip_nr_state {
 } x264hip_nr_state;
 int  x264hip_nr_state_alloc(x264hip_frame_ctx *c, x264hip_nr_state *nr);
 void x264hip_nr_state_free(x264hip_frame_ctx *c, x264hip_nr_state *nr);
-/* x264_noise_reduction_update (R/encoder/macroblock.c:890-911) for every chain: call once after each frame's sweep */
+/* The sweep adds to sum / count in the final encode of every inter macroblock (x264_macroblock_encode with h->mb.b_noise_reduction), in P
+ * and in B slices alike: B_DIRECT and every B partition, 16 per macroblock coded with the 4x4 transform, 4 per macroblock with the 8x8
+ * one.  Skip probes, the trial encodes of the RD levels and intra macroblocks neither denoise nor add.  The sums belong to a chain, not
+ * to a frame: a chain's sweeps and updates must stay in order on one stream.
+ *
+ * x264_noise_reduction_update (R/encoder/macroblock.c:890-911) for every chain: call once after each frame's sweep when every chain of
+ * the batch coded a frame in it (lock step) */
 int  x264hip_noise_reduction_update(x264hip_frame_ctx *c, const x264hip_nr_state *nr, int noise_reduction);
+/* The same for the n_chains chains listed in chains_dev (device memory, one block per entry; enqueued on the context's stream, which
+ * reads the list then): for batches whose chains do not all finish a frame per launch.  The reference updates once per RETURNED frame
+ * (R/encoder/encoder.c:1755): after a given-up attempt was coded again, never between the attempts -- the given-up attempt's additions
+ * stay in the sums -- and not at all for a chain that coded nothing.  The update is not idempotent (it halves sums and counts above a
+ * threshold), so the other chains are left bit for bit as they are.  An index outside the batch inside the list is skipped.  Refused
+ * before any launch: no state, n_chains < 0 or above the batch, n_chains > 0 without a list.  n_chains = 0 enqueues nothing */
+int  x264hip_noise_reduction_update_chains(x264hip_frame_ctx *c, const x264hip_nr_state *nr, int noise_reduction, const int *chains_dev, int n_chains);
 
 int  x264hip_mb_state_alloc(x264hip_frame_ctx *c, x264hip_mb_state *st);
 #define X264HIP_STATE_NO_LEVELS 1   /* luma / luma_dc / chroma_dc / chroma_ac stay NULL: for sweeps that write the payload themselves (rd.write) */

@@ -291,6 +291,7 @@ PROTOTYPES = {
     "x264hip_nr_state_alloc": "i:pp",
     "x264hip_nr_state_free": "v:pp",
     "x264hip_noise_reduction_update": "i:ppi",
+    "x264hip_noise_reduction_update_chains": "i:ppipi",
     "x264hip_mb_state_alloc": "i:pp",
     "x264hip_mb_state_alloc_ex": "i:ppi",
     "x264hip_mb_state_free": "v:pp",

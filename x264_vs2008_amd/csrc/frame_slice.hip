@@ -66,10 +66,10 @@ extern "C" void x264hip_mb_state_free(x264hip_frame_ctx *c, x264hip_mb_state *st
 static __constant__ u16 c_nr_w4[16] = {800, 320, 800, 320, 320, 128, 320, 128, 800, 320, 800, 320, 320, 128, 320, 128};        // x264_dct4_weight2_tab
 static __constant__ u16 c_nr_w8k[6] = {256, 201, 656, 227, 410, 363};                                                     // x264_dct8_weight2_tab's W(i)
 static __constant__ u8 c_nr_k8[32] = {0, 3, 4, 3, 0, 3, 4, 3, 3, 1, 5, 1, 3, 1, 5, 1, 4, 5, 2, 5, 4, 5, 2, 5, 3, 1, 5, 1, 3, 1, 5, 1};
-__global__ __launch_bounds__(128) void k_nr_update(u32 *sum, u32 *count, u16 *offset, int strength)
+__device__ __forceinline__ void nr_update_chain(u32 *sum, u32 *count, u16 *offset, int chain, int strength)
 {
     const int cat = threadIdx.x >> 6, i = threadIdx.x & 63, size = cat ? 64 : 16;
-    sum += (size_t)blockIdx.x * 128; count += (size_t)blockIdx.x * 2; offset += (size_t)blockIdx.x * 128;
+    sum += (size_t)chain * 128; count += (size_t)chain * 2; offset += (size_t)chain * 128;
     u32 cnt = count[cat], sv = i < size ? sum[cat * 64 + i] : 0;
     const bool halve = cnt > (cat ? (1u << 16) : (1u << 18));
     __syncthreads();                                   // everyone has read the count before it is rewritten
@@ -78,6 +78,19 @@ __global__ __launch_bounds__(128) void k_nr_update(u32 *sum, u32 *count, u16 *of
         const unsigned long long w = cat ? c_nr_w8k[c_nr_k8[i & 31]] : c_nr_w4[i];
         offset[cat * 64 + i] = (u16)(((unsigned long long)strength * cnt + sv / 2) / ((unsigned long long)sv * w / 256 + 1));
     }
+}
+__global__ __launch_bounds__(128) void k_nr_update(u32 *sum, u32 *count, u16 *offset, int strength)
+{
+    nr_update_chain(sum, count, offset, (int)blockIdx.x, strength);
+}
+// the same for the chains a device list names (one block per entry): a chain that coded no frame keeps its sums, counts and offsets
+// as they are -- a second halving is not the first one's repeat once a count is above twice its threshold.  An index outside the
+// batch writes nothing (block-uniform: the whole block leaves before the barrier)
+__global__ __launch_bounds__(128) void k_nr_update_chains(u32 *sum, u32 *count, u16 *offset, int strength, const int *chains, int batch)
+{
+    const int chain = chains[blockIdx.x];
+    if (chain < 0 || chain >= batch) return;
+    nr_update_chain(sum, count, offset, chain, strength);
 }
 static int nr_alloc_arrays(x264hip_frame_ctx *c, x264hip_nr_state *nr)
 {
@@ -109,6 +122,16 @@ extern "C" int x264hip_noise_reduction_update(x264hip_frame_ctx *c, const x264hi
     HIPCHK(hipGetLastError());
     return 0;
 }
+extern "C" int x264hip_noise_reduction_update_chains(x264hip_frame_ctx *c, const x264hip_nr_state *nr, int noise_reduction, const int *chains_dev, int n_chains)
+{
+    if (!nr || !nr->sum || !nr->count || !nr->offset) { set_error("noise_reduction_update_chains: no state"); return -1; }
+    if (n_chains < 0 || n_chains > c->batch) { set_error("noise_reduction_update_chains: %d chains of a batch of %d", n_chains, c->batch); return -1; }
+    if (n_chains > 0 && !chains_dev) { set_error("noise_reduction_update_chains: %d chains without a list", n_chains); return -1; }
+    if (!n_chains) return 0;
+    hipLaunchKernelGGL(k_nr_update_chains, dim3((unsigned)n_chains), dim3(128), 0, c->stream, nr->sum, nr->count, nr->offset, noise_reduction, chains_dev, c->batch);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
 
 // The three argument structures of one sweep launch from the ABI's description of it, and which kernel codes it (sweep_tables.h)
 static void sweep_note_frame(const x264hip_slice_params *p, int n_refs, x264hip_mb_state *out);
@@ -127,7 +150,8 @@ static int sweep_build(x264hip_frame_ctx *c, const x264hip_picture *fenc, const 
         // x264hip_cavlc_write_frame / _chains write it from the state
         const bool b_cavlc = !p->cabac && !p->rd->write && p->subme <= 5;
         if (p->subme < 2 || p->subme > 8 || (!b_cavlc && (!p->rd->write || !p->cabac))) { set_error("slice_sweep: B slices are built for subme 2..8 with the CABAC writer in the loop, and for subme 2..5 without a writer (cabac = 0, rd.write = 0: a CAVLC slice, written from the state afterwards); subme 9 refines a B macroblock's vectors by RD: x264_me_refine_bidir_rd, not built"); return -1; }
-        if (p->noise_reduction || p->lossless) { set_error("slice_sweep: B slices with --nr / lossless are not built"); return -1; }
+        // (--nr in a B slice: the final encode of an inter macroblock is the P slices' own, slice_sweep_body.h encode_mb)
+        if (p->lossless) { set_error("slice_sweep: lossless B slices are not built (x264_validate_parameters turns B frames off at QP 0)"); return -1; }
         if (!out->mv1 || !pb->l1_state->mb_type) { set_error("slice_sweep: mb_state without list-1 arrays"); return -1; }
     }
     if (p->qp < 0 || p->qp > 51) { set_error("slice_sweep: qp out of range"); return -1; }

@@ -23,7 +23,9 @@ checks) -- ABR / VBV / 2-pass, --direct none, --no-cabac with --subme 6 and abov
 Every coded frame is measured as x264 does by default (PSNR, SSIM, macroblock statistics: --no-psnr / --no-ssim / --quiet turn that off, -v prints
 x264_encoder_frame_end's line per frame) and x264_encoder_close's report goes to stderr at the end, one per stream; the `.264` bytes do not depend on it.
 Scene cuts work as in the reference: by default after the fact (a P picture that should have been intra is coded again, encoder.c:1603-1699), with
---pre-scenecut in the lookahead."""
+--pre-scenecut in the lookahead.  --nr N goes with all of it -- B frames, adaptive B placement, --direct auto, --no-cabac, the RD levels, trellis,
+adaptive quantisation and either scene cut: x264_noise_reduction_update runs once per returned frame of a stream, behind a given-up attempt's second
+encode as in the reference (stream.py: _nr_update).  Lossless turns it off, as x264_validate_parameters does."""
 import argparse
 import os
 import re

@@ -210,6 +210,8 @@ class ChainEncoder:
                 raise ValueError("lanes: B frames run in the raster variant")
             if direct_pred == 2:
                 raise ValueError("lanes: temporal direct prediction chains every frame to the one coded before it (x264hip_slice_rd.stale)")
+            if noise_reduction:
+                raise ValueError("lanes: --nr chains every frame to the one coded before it (x264hip_nr_state: its sums and the update behind every frame)")
             if self.psy_trellis_fix:
                 raise ValueError("lanes: psy-trellis chains every frame to the one coded before it (x264hip_slice_rd.psy_carry)")
             d = self.ctx.dims

@@ -108,6 +108,8 @@ class StreamEncoder(ChainEncoder):
         self.tab_host = lib.x264hip_host_alloc(tb * B)
         self.tab_dev = DeviceArray(lib, (tb * B,), np.uint8)
         self.elems_dev = [DeviceArray(lib, (B,), np.int32) for _ in range(len(self.pool))]
+        # --nr: the chains that coded a frame for good in a step, for x264hip_noise_reduction_update_chains (_nr_update)
+        self.nr_chains_dev = DeviceArray(lib, (B,), np.int32) if self.nr else None
         self.cv_host, self.cv_dev, self._cv = None, None, []       # the table of x264hip_cavlc_write_chains; what _entry notes for it
         if self.cavlc:
             cvb = lib.x264hip_chain_cavlc_bytes()
@@ -132,9 +134,6 @@ class StreamEncoder(ChainEncoder):
         if self.post_scenecut:
             if o["keyint"] <= 0:
                 raise ValueError("StreamEncoder: the post-encode scene cut needs a finite keyint")
-            if o["noise_reduction"]:
-                raise ValueError("StreamEncoder: --nr with the post-encode scene cut: a given-up attempt has already added to the noise-reduction sums "
-                                 "(the reference's has too, but per frame, not per batch); run with pre_scenecut=1")
             self.stats_dev = [DeviceArray(lib, (B, 32), np.uint8) for _ in self.pool]
         self.sweep_events = None       # set to [] to collect (start, stop, chains, algorithmic bytes) HIP events around every step's sweep launches
         # psnr / ssim (ChainEncoder's options): ONE quality pass per launch over the chains that coded a frame, behind the kept frames' loop filter
@@ -182,6 +181,7 @@ class StreamEncoder(ChainEncoder):
             return []
         out = self._sweep(frames)
         if not self.post_scenecut:
+            self._nr_update(out)
             if pipelined and not self.flushing:
                 self._prep = self._prepare(fill)        # beside the sweep just launched
             return out
@@ -225,7 +225,21 @@ class StreamEncoder(ChainEncoder):
             self.src_ctx.sync()
             for ci in redone:
                 self._prep[ci] = nxt[ci]
+        self._nr_update(out)
         return out
+
+    def _nr_update(self, out):
+        """x264_noise_reduction_update for the chains that coded a frame for good in this step (encoder.c:1755: once per returned frame, behind
+        the `goto do_encode` of a given-up attempt, whose additions to the sums stay): one call behind the step's last sweep, none between the
+        attempts, and a chain that coded nothing keeps its tables as they are (the update halves: it is not idempotent)."""
+        if not self.nr or not out:
+            return
+        c = self.ctx
+        lst = np.zeros(c.batch, np.int32)
+        lst[:len(out)] = [cd.chain for cd in out]
+        self.nr_chains_dev.set(lst)
+        c.check(self.lib.x264hip_noise_reduction_update_chains(c.h, C.byref(self.nr), self.opt["noise_reduction"], self.nr_chains_dev.p, len(out)),
+                "noise_reduction_update_chains")
 
     def _sweep(self, frames):
         """The chain-table launch for the chains that have a frame in `frames` (per chain an x264hip_look_frame or None), then the filters of the kept ones."""
@@ -306,8 +320,6 @@ class StreamEncoder(ChainEncoder):
             for k, (ci, mine, cp) in enumerate(self._cv):
                 cv[k] = ChainCavlc(ci, C.addressof(mine), C.addressof(cp))
             c.check(L.x264hip_cavlc_write_chains(c.h, cv, len(self._cv), self.cv_host, self.cv_dev.p), "cavlc_write_chains")
-        if self.nr:                                        # x264_noise_reduction_update at the end of every frame (encoder.c:1755)
-            c.check(L.x264hip_noise_reduction_update(c.h, C.byref(self.nr), self.opt["noise_reduction"]), "noise_reduction_update")
         for pic_i, chains in filt.items():
             c.check(L.x264hip_frame_ctx_elements(c.h, publish(pic_i, chains), len(chains)), "frame_ctx_elements")
             self.filter_kept(c, self.pool[pic_i], self.states[pic_i].st)
@@ -450,7 +462,7 @@ class StreamEncoder(ChainEncoder):
         for pair in self.aq_slots or []:
             for a in pair:
                 a.free()
-        for a in [self.tab_dev] + self.elems_dev + (self.stats_dev or []) + ([self.dscore_dev] if self.dscore_dev else []) + ([self.cv_dev] if self.cv_dev else []):
+        for a in [self.tab_dev] + self.elems_dev + ([self.nr_chains_dev] if self.nr_chains_dev else []) + (self.stats_dev or []) + ([self.dscore_dev] if self.dscore_dev else []) + ([self.cv_dev] if self.cv_dev else []):
             a.free()
         if self.cv_host:
             self.lib.x264hip_host_free(self.cv_host)
@@ -485,7 +497,9 @@ class AsyncStreamEncoder(StreamEncoder):
         if n_frames is None:
             raise ValueError("AsyncStreamEncoder: n_frames (pictures per chain) is needed")
         if kw.get("noise_reduction"):
-            raise ValueError("AsyncStreamEncoder: --nr updates its tables once per frame for all chains together: lock-step only")
+            raise ValueError("AsyncStreamEncoder: --nr: a launch's B kernel ends on a stream of its own, and a chain's noise-reduction sums must be "
+                             "complete before its update (x264hip_noise_reduction_update_chains) and the update before the chain's next sweep: that "
+                             "ordering is not built here; StreamEncoder and ChainEncoder code --nr")
         bf = kw.get("bframes", 0)
         b_adapt = kw.get("b_adapt", 1)
         delay = (max(bf, 3) * 4 if b_adapt == 2 and bf else bf)
