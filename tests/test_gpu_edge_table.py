@@ -1,4 +1,4 @@
-"""GPU: x264hip_slice_sweep_chains -- the chain table's own kernels (frame_slice_ch_rd / _ch_rf / _ll_ch / _ll_ch_rf.hip) -- on pictures of
+"""GPU: x264hip_slice_sweep_chains -- the chain table's own kernels (frame_slice_rd_ch / _rf_ch / _ll_ch / _ll_rf_ch.hip) -- on pictures of
 one to six macroblocks.  StreamEncoder cannot reach them at these sizes (x264hip_lookahead_cost_frames refuses mb_w <= 2 or mb_h <= 2), so
 the launches are tests/table_util.py's.  Nine I / P chains = the nine contents of tests/edge_cases.py in one table; the lossy tables give
 chain b the QP (8, 26, 51)[b % 3], the lossless ones QP 0 throughout (a table is all-lossless or not at all).  Expected, bit for bit: the

@@ -1,6 +1,7 @@
-// frame_slice.hip -- host side of the macroblock sweep (x264hip_slice_sweep_frame ...) and the wavefront-schedule kernel variants.
-// The kernel itself lives in slice_kernel.h; its raster-order variant is instantiated in frame_slice_rd.hip (a translation unit of
-// its own so that the two compile side by side).
+// frame_slice.hip -- host side of the macroblock sweep (x264hip_slice_sweep_frame ...) and the wavefront-schedule kernel variants
+// (x264hip_launch_slice_plain).  The kernel itself lives in slice_kernel.h; its raster-order variants are instantiated in
+// frame_slice_<kind>.hip and frame_slice_<kind>_ch.hip (translation units of their own so that they all compile side by side), and
+// sweep_tables.h says which of them a sweep is launched with.
 #include <vector>
 #include "slice_kernel.h"
 #include "x264hip_lookahead.h"
@@ -274,7 +275,6 @@ static int sweep_build(x264hip_frame_ctx *c, const x264hip_picture *fenc, const 
         for (int i = 0; i < SW_MAX_REFS; i++) { t.biw[i] = 32; t.dsf[i] = 256; t.map_col[i] = -2; }
     }
     memset(&r, 0, sizeof(r));
-    kind = SW_KIND_PLAIN;
     if (prd) {
         r.on = 1; r.mbrd = mbrd; r.trellis = p->cabac ? prd->trellis : 0; r.psy_rd = mbrd ? prd->psy_rd : 0;
         r.write = prd->write; r.cabac_init_idc = prd->cabac_init_idc; r.i_frame = prd->i_frame; r.i_frame_stride = prd->i_frame_stride;
@@ -291,13 +291,9 @@ static int sweep_build(x264hip_frame_ctx *c, const x264hip_picture *fenc, const 
             r.direct_score = pb->direct_score;
             r.mv1 = out->mv1; r.ref1 = (signed char *)out->ref1; r.mvr1 = out->mvr1; r.mvd1 = out->mvd1; r.skipbp = out->skipbp;
             r.col_type = (const signed char *)pb->l1_state->mb_type; r.col_ref = (const signed char *)pb->l1_state->ref; r.col_mv = pb->l1_state->mv;
-            // the extended B kernel (temporal direct prediction, the lookahead's candidates) only where it is needed: the plain one is 6-8 % faster
-            kind = r.direct_temporal || r.direct_score || a.lowres0 || a.lowres1 ? SW_KIND_BT : SW_KIND_B;
-        } else if (a.lossless)
-            kind = mbrd >= 2 ? SW_KIND_LL_RF : SW_KIND_LL;  // kernels of their own (k_lossless_raster)
-        else
-            kind = mbrd >= 2 ? SW_KIND_RF : SW_KIND_RD;     // subme 8-9: the I / P kernel with the RD refinement (slice_refine.h)
+        }
     }
+    kind = sweep_kind(prd != nullptr, is_b, a.lossless, mbrd, r.psy_trellis != 0, r.direct_temporal || r.direct_score || a.lowres0 || a.lowres1);
     return 0;
 }
 
@@ -313,6 +309,24 @@ static void sweep_note_frame(const x264hip_slice_params *p, int n_refs, x264hip_
     }
 }
 
+// the PLAIN kind's launch: the wavefront schedule, one wavefront per macroblock row of every chain (padded to whole groups of 8 chains)
+void x264hip_launch_slice_plain(const SwArgs &a, const SwRefs &t, const SwRd &r, hipStream_t stream)
+{
+    static int wpe = 0;
+    if (!wpe) {                                                      // developer knob: X264HIP_SWEEP_WPE = 1..3
+        const char *e = getenv("X264HIP_SWEEP_WPE");
+        wpe = e ? atoi(e) : 3;                                       // 3 waves/SIMD (168 VGPRs, 12 waves per CU with 13 KB of LDS each): measured best
+        if (wpe < 1 || wpe > 3) wpe = 3;
+    }
+    const dim3 grid((unsigned)(a.batch_pad * a.mb_h)), block(64);
+    switch (a.lossless ? 0 : wpe) {
+    case 0: hipLaunchKernelGGL((k_slice_sweep<2, true>), grid, block, 0, stream, a, t, r, nullptr); break;
+    case 1: hipLaunchKernelGGL(k_slice_sweep<1>, grid, block, 0, stream, a, t, r, nullptr); break;
+    case 3: hipLaunchKernelGGL(k_slice_sweep<3>, grid, block, 0, stream, a, t, r, nullptr); break;
+    default: hipLaunchKernelGGL(k_slice_sweep<2>, grid, block, 0, stream, a, t, r, nullptr); break;
+    }
+}
+
 extern "C" int x264hip_slice_sweep_frame(x264hip_frame_ctx *c, const x264hip_picture *fenc, const x264hip_picture *const *refs, int n_refs,
                                          x264hip_picture *recon, const x264hip_slice_params *p, const x264hip_mb_state *l0,
                                          x264hip_mb_state *out)
@@ -320,25 +334,9 @@ extern "C" int x264hip_slice_sweep_frame(x264hip_frame_ctx *c, const x264hip_pic
     SwArgs a; SwRefs t; SwRd r;
     int kind;
     if (sweep_build(c, fenc, refs, n_refs, recon, p, l0, out, a, t, r, kind)) return -1;
-    const bool is_p = p->slice_type == 0;
     HIPCHK(hipMemsetAsync(out->progress, 0, state_progress_bytes(c->d.mb_h, c->batch), c->stream));
-    static int wpe = 0;
-    if (!wpe) {                                                      // developer knob: X264HIP_SWEEP_WPE = 1..3
-        const char *e = getenv("X264HIP_SWEEP_WPE");
-        wpe = e ? atoi(e) : 3;                                       // 3 waves/SIMD (168 VGPRs, 12 waves per CU with 13 KB of LDS each): measured best
-        if (wpe < 1 || wpe > 3) wpe = 3;
-    }
-    if (k_sweep_kinds[kind].frame) k_sweep_kinds[kind].frame(a, t, r, c->stream);
-    else {
-        const dim3 grid((unsigned)(a.batch_pad * a.mb_h)), block(64);
-        switch (a.lossless ? 0 : wpe) {
-        case 0: hipLaunchKernelGGL((k_slice_sweep<2, true>), grid, block, 0, c->stream, a, t, r, nullptr); break;
-        case 1: hipLaunchKernelGGL(k_slice_sweep<1>, grid, block, 0, c->stream, a, t, r, nullptr); break;
-        case 3: hipLaunchKernelGGL(k_slice_sweep<3>, grid, block, 0, c->stream, a, t, r, nullptr); break;
-        default: hipLaunchKernelGGL(k_slice_sweep<2>, grid, block, 0, c->stream, a, t, r, nullptr); break;
-        }
-    }
-    if (kind == SW_KIND_PLAIN && is_p && a.flags_intra)
+    k_sweep_kinds[kind].frame(a, t, r, c->stream);
+    if (kind == SW_KIND_PLAIN && p->slice_type == 0 && a.flags_intra)
         hipLaunchKernelGGL(k_resolve_fast_intra, dim3(c->batch), dim3(64), 0, c->stream, (const signed char *)out->mb_type, out->cost_intra,
                            (const int *)out->cost_intra_alt, c->d.mb_w * c->d.mb_h);
     HIPCHK(hipGetLastError());
@@ -346,7 +344,6 @@ extern "C" int x264hip_slice_sweep_frame(x264hip_frame_ctx *c, const x264hip_pic
     return 0;
 }
 
-thread_local bool sw_table_psy = false;
 // The chain-table launch: every entry is a sweep of ONE chain (batch element) with its own pictures, states and slice parameters.
 static int sweep_chains(x264hip_frame_ctx *c, x264hip_chain_sweep *e, int n, void *staging_host, void *table_dev, void *ev_ip, void *ev_b, bool join);
 static int b_events(x264hip_frame_ctx *c)
@@ -387,7 +384,7 @@ static int sweep_chains(x264hip_frame_ctx *c, x264hip_chain_sweep *e, int n, voi
     if (!staging_host || !table_dev) { set_error("slice_sweep_chains: staging / table buffers missing"); return -1; }
     SwDesc *st = (SwDesc *)staging_host;
     // entries sorted by kind (sweep_tables.h): a first pass builds, a second places
-    int cnt[SW_N_KINDS] = {0}, n_cavlc = 0, n_psy = 0;
+    int cnt[SW_N_KINDS] = {0}, n_cavlc = 0;
     static thread_local std::vector<SwDesc> tmp;
     static thread_local std::vector<int> kinds;
     tmp.resize((size_t)n); kinds.resize((size_t)n);
@@ -400,18 +397,19 @@ static int sweep_chains(x264hip_frame_ctx *c, x264hip_chain_sweep *e, int n, voi
         if (sweep_build(c, s.fenc, s.refs, s.n_refs, s.recon, s.params, s.l0, s.out, tmp[i].a, tmp[i].t, tmp[i].r, kind)) return -1;
         kind = k_sweep_kinds[kind].in_table;
         tmp[i].a.chain = s.chain;
-        kinds[i] = kind; cnt[kind]++; n_psy += tmp[i].r.psy_trellis != 0;
+        kinds[i] = kind; cnt[kind]++;
         sweep_note_frame(s.params, s.n_refs, s.out);
     }
     // one launch is all-lossless or not at all: QP 0 changes what every table and buffer of a chain means (SPS profile, payload bound,
     // SAD lookahead), so a table that mixes the two is a caller's mistake, not a schedule
-    const int n_ll = cnt[SW_KIND_LL] + cnt[SW_KIND_LL_RF];
-    if (n_ll && n_ll != n) { set_error("slice_sweep_chains: %d of %d entries are lossless (QP 0): a chain table is all-lossless or not at all", n_ll, n); return -1; }
+    int n_mixed = 0;
+    const int mixed = sweep_mixed_family(cnt, &n_mixed);
+    if (mixed == SW_LOSSLESS) { set_error("slice_sweep_chains: %d of %d entries are lossless (QP 0): a chain table is all-lossless or not at all", n_mixed, n); return -1; }
     // ... and all-CAVLC or not at all: the caller follows the launch with ONE x264hip_cavlc_write_chains over the same chains, and a CABAC
     // chain's payload slot already holds its slice then
     if (n_cavlc && n_cavlc != n) { set_error("slice_sweep_chains: %d of %d entries are CAVLC slices without a writer (cabac = 0, rd.write = 0): a chain table is all-CAVLC or not at all", n_cavlc, n); return -1; }
     // ... and all-psy-trellis or not at all: its kernels are others (k_psy_raster), one launch per kind, and the strength is a setting of the whole encode
-    if (n_psy && n_psy != n) { set_error("slice_sweep_chains: %d of %d entries have psy-trellis on: a chain table is all-psy-trellis or not at all", n_psy, n); return -1; }
+    if (mixed == SW_PSY) { set_error("slice_sweep_chains: %d of %d entries have psy-trellis on: a chain table is all-psy-trellis or not at all", n_mixed, n); return -1; }
     int base[SW_N_KINDS], at[SW_N_KINDS];
     sweep_place(cnt, base);
     memcpy(at, base, sizeof(at));
@@ -420,7 +418,7 @@ static int sweep_chains(x264hip_frame_ctx *c, x264hip_chain_sweep *e, int n, voi
     const SwDesc *tab = (const SwDesc *)table_dev;
     // The I / P chains and the B chains of a step are different chains: their kernels run side by side, the B kernel on a stream of its
     // own between two events (behind the table's upload, ahead of whatever follows on the context's stream).
-    const bool two = cnt[SW_KIND_BT] && (cnt[SW_KIND_RD] || cnt[SW_KIND_RF] || !join);
+    const bool two = sweep_two_streams(cnt, join);
     if (two) {
         if (!c->b_stream) { HIPCHK(hipStreamCreateWithFlags(&c->b_stream, hipStreamNonBlocking)); c->own_b_stream = true; }
         if (b_events(c)) return -1;
@@ -428,9 +426,7 @@ static int sweep_chains(x264hip_frame_ctx *c, x264hip_chain_sweep *e, int n, voi
         HIPCHK(hipStreamWaitEvent(c->b_stream, c->b_ready, 0));
     }
     const hipStream_t b_stream = two ? c->b_stream : c->stream;
-    sw_table_psy = n_psy != 0;                         // what the launch functions cannot read from the device's table
     sweep_enqueue(tab, cnt, base, c->stream, b_stream);
-    sw_table_psy = false;
     if (two && join) {
         HIPCHK(hipEventRecord(c->b_done, c->b_stream));
         HIPCHK(hipStreamWaitEvent(c->stream, c->b_done, 0));

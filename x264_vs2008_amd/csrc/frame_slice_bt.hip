@@ -5,8 +5,4 @@
 // keeps its registers: with either addition inside it the B launches ran 6-8 % slower.
 #include "slice_kernel.h"
 
-void x264hip_launch_slice_bt(const SwArgs &a, const SwRefs &t, const SwRd &r, hipStream_t stream)
-{
-    if (r.psy_trellis) { x264hip_launch_psy_bt(a, t, r, stream); return; }
-    hipLaunchKernelGGL((k_slice_sweep<2, false, true, true, true>), dim3((unsigned)a.batch), dim3(64), 0, stream, a, t, r, nullptr);
-}
+void x264hip_launch_slice_bt(const SwArgs &a, const SwRefs &t, const SwRd &r, hipStream_t stream) { sw_launch_frame(k_slice_sweep<2, false, true, true, true>, a, t, r, stream); }

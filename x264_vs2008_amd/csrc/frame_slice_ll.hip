@@ -3,7 +3,4 @@
 // raster kernels stay the instantiations they were.
 #include "slice_kernel.h"
 
-void x264hip_launch_slice_ll(const SwArgs &a, const SwRefs &t, const SwRd &r, hipStream_t stream)
-{
-    hipLaunchKernelGGL((k_lossless_raster<false, false>), dim3((unsigned)a.batch), dim3(64), 0, stream, a, t, r, nullptr);
-}
+void x264hip_launch_slice_ll(const SwArgs &a, const SwRefs &t, const SwRd &r, hipStream_t stream) { sw_launch_frame(k_lossless_raster<false, false>, a, t, r, stream); }

@@ -2,7 +2,4 @@
 // wave per SIMD: the refinement's state on top of the analysis records lives in registers, not in scratch memory.
 #include "slice_kernel.h"
 
-void x264hip_launch_slice_ll_rf(const SwArgs &a, const SwRefs &t, const SwRd &r, hipStream_t stream)
-{
-    hipLaunchKernelGGL((k_lossless_raster<true, false>), dim3((unsigned)a.batch), dim3(64), 0, stream, a, t, r, nullptr);
-}
+void x264hip_launch_slice_ll_rf(const SwArgs &a, const SwRefs &t, const SwRd &r, hipStream_t stream) { sw_launch_frame(k_lossless_raster<true, false>, a, t, r, stream); }

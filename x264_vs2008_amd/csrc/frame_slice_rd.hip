@@ -2,8 +2,4 @@
 // chain walks the whole frame, with the RD levels, trellis, adaptive quantisation and the CABAC coder inside the loop.
 #include "slice_kernel.h"
 
-void x264hip_launch_slice_rd(const SwArgs &a, const SwRefs &t, const SwRd &r, hipStream_t stream)
-{
-    if (r.psy_trellis) { x264hip_launch_psy_rd(a, t, r, stream); return; }
-    hipLaunchKernelGGL((k_slice_sweep<2, false, true>), dim3((unsigned)a.batch), dim3(64), 0, stream, a, t, r, nullptr);
-}
+void x264hip_launch_slice_rd(const SwArgs &a, const SwRefs &t, const SwRd &r, hipStream_t stream) { sw_launch_frame(k_slice_sweep<2, false, true>, a, t, r, stream); }

@@ -4,8 +4,4 @@
 // (subme <= 7) kernel nothing.
 #include "slice_kernel.h"
 
-void x264hip_launch_slice_rf(const SwArgs &a, const SwRefs &t, const SwRd &r, hipStream_t stream)
-{
-    if (r.psy_trellis) { x264hip_launch_psy_rf(a, t, r, stream); return; }
-    hipLaunchKernelGGL((k_slice_sweep<2, false, true, false, false, true>), dim3((unsigned)a.batch), dim3(64), 0, stream, a, t, r, nullptr);
-}
+void x264hip_launch_slice_rf(const SwArgs &a, const SwRefs &t, const SwRd &r, hipStream_t stream) { sw_launch_frame(k_slice_sweep<2, false, true, false, false, true>, a, t, r, stream); }

@@ -1496,13 +1496,22 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1))) void k_
     constexpr bool LL = false, RD = true, PT = true;
 #include "slice_sweep_body.h"
 }
-// its launch functions (frame_slice_psy_*.hip), called by the launch functions of the kinds below when SwRd::psy_trellis is set; a chain-table
-// launch function sees only the device's table, so x264hip_slice_sweep_chains says which by sw_table_psy around its launches
-typedef void SwLaunchPsy(const SwArgs &a, const SwRefs &t, const SwRd &r, hipStream_t stream);
-typedef void SwLaunchPsyChains(const struct SwDesc *tab, int n, hipStream_t stream);
-SwLaunchPsy x264hip_launch_psy_rd, x264hip_launch_psy_rf, x264hip_launch_psy_bt;
-SwLaunchPsyChains x264hip_launch_psy_rd_ch, x264hip_launch_psy_rf_ch, x264hip_launch_psy_bt_ch;
-extern thread_local bool sw_table_psy;
 
-// the launch functions of the instantiation files (frame_slice_*.hip) and the table of kinds the host side walks
+// The two launches of the raster kernels.  Every instantiation has a translation unit of its own (frame_slice_<kind>.hip the lock-step
+// launch, frame_slice_<kind>_ch.hip the chain-table one) so that the kernels compile side by side; each of them names its kernel here.
+typedef void SwKernel(SwArgs, SwRefs, SwRd, const SwDesc *);
+// lock-step: one block per chain of the batch, all of them with the arguments of the launch
+static inline void sw_launch_frame(SwKernel *kernel, const SwArgs &a, const SwRefs &t, const SwRd &r, hipStream_t stream)
+{
+    hipLaunchKernelGGL(kernel, dim3((unsigned)a.batch), dim3(64), 0, stream, a, t, r, nullptr);
+}
+// chain table: block i takes its arguments from tab[i] (CH), and the launch's own are dummies
+static inline void sw_launch_chains(SwKernel *kernel, const SwDesc *tab, int n, hipStream_t stream)
+{
+    SwArgs a; SwRefs t; SwRd r;
+    memset(&a, 0, sizeof(a)); memset(&t, 0, sizeof(t)); memset(&r, 0, sizeof(r));
+    hipLaunchKernelGGL(kernel, dim3((unsigned)n), dim3(64), 0, stream, a, t, r, tab);
+}
+
+// the launch functions of the instantiation files, and the table of kinds in which the host side finds them
 #include "sweep_tables.h"
