@@ -68,8 +68,8 @@ int x264hip_frame_ctx_elements(x264hip_frame_ctx *c, const int *elems_dev, int n
  * [batch][payload_cap] bytes, chain b's slice_data() starts X264HIP_PAYLOAD_LEAD (64) bytes into its slot, from bit 0, rbsp trailing bits
  * included; payload_len: device [batch] int32; mb_bits (optional): device [batch][n_mb], bit position after every macroblock.
  * Asynchronous on the context's stream.  I_PCM macroblocks and a slot too small end with x264hip_slice_sweep_status reporting an abort:
- * an I or P slice of x264hip_cavlc_write_frame stops 1024 bytes before its slot's end (payload_cap >= 4096), a B slice and every slice of
- * x264hip_cavlc_write_chains before a macroblock whose worst case (2624 bytes, derived in csrc/frame_cavlc.hip) might not fit. */
+ * every slice, of x264hip_cavlc_write_frame (payload_cap >= 4096) and of x264hip_cavlc_write_chains alike, stops before a macroblock whose
+ * worst case (2624 bytes, derived and measured in csrc/frame_cavlc.hip) might not fit. */
 typedef struct {
     int slice_type;            /* 0 P, 1 B, 2 I */
     int n_ref0;                /* h->mb.pic.i_fref[0]: references of list 0 (the number te() is written against) */

@@ -202,6 +202,11 @@ static int setup_encoder(rctx *c, const refslice_params *p, const refslice_ext *
     h->sps->b_direct8x8_inference = 1;                   /* x264_sps_init, R/encoder/set.c:136 */
     n = h->mb.i_mb_count = mb_w * mb_h;
     h->pps->b_cabac = p->cabac; h->pps->b_transform_8x8_mode = h->param.analyse.b_transform_8x8;
+    /* the profile as x264_sps_init chooses it (R/encoder/set.c:81-89): the CAVLC writer reads it where a level code passes 4095 -- High
+     * profile lets the prefix grow, below it the code is clipped (R/encoder/cavlc.c:83-104).  Left at 0 every such level was clipped. */
+    h->sps->i_profile_idc = h->param.rc.i_rc_method == X264_RC_CQP && p->qp == 0 ? PROFILE_HIGH444_PREDICTIVE
+                          : h->param.analyse.b_transform_8x8 || p->cqm_preset ? PROFILE_HIGH
+                          : p->cabac || h->param.i_bframe > 0 ? PROFILE_MAIN : PROFILE_BASELINE;
     for (i = 0; i < 6; i++) h->pps->scaling_list[i] = p->cqm_preset ? x264_cqm_jvt[i] : flat16;   /* x264_pps_init, R/encoder/set.c */
     h->param.i_cqm_preset = p->cqm_preset;
     h->chroma_qp_table = i_chroma_qp_table + 12 + h->param.analyse.i_chroma_qp_offset;

@@ -41,7 +41,13 @@ CASES = {
     "aq_empty_i16": dict(size=(96, 80), n=4, clip=("stripes", 1), ext=dict(aq_mode=1, aq_strength=0.8), twin_write=1,
                          kw=dict(P13, qp=30, subme=5, n_refs=2, transform8x8=1, keyint=2)),
 }
-LIVE_CLIPS = {("stripes", 1): ("stripes", 2), ("synth", 0): ("synth", 37), ("synth", 9): ("synth", 21), ("synth", 3): ("synth", 50), ("synth", 5): ("synth", 14),
+# lossy QP 1 (I slices at QP 0, not lossless): levels beyond 2900, deep in the Exp-Golomb tail of coeff_abs_level_minus1 -- edge_cases.MED at the
+# smallest and the largest tiny picture on the three contents with the largest levels
+QP1_SIZES, QP1_KINDS = ((40, 24), (16, 16)), ("checker", "noise", "satnoise")
+QP1_KW = dict(ec.MED, qp=1, subme=5)
+QP1_LEVEL = 2900
+CASES.update({"qp1_%dx%d_%s" % (s + (k,)): dict(size=s, n=3, clip=("edge", k), kw=QP1_KW) for s in QP1_SIZES for k in QP1_KINDS})
+LIVE_CLIPS = {("edge", "checker"): ("edge", "vstripe"), ("edge", "satnoise"): ("edge", "flip"), ("stripes", 1): ("stripes", 2), ("synth", 0): ("synth", 37), ("synth", 9): ("synth", 21), ("synth", 3): ("synth", 50), ("synth", 5): ("synth", 14),
               ("edge", "ramp"): ("edge", "checker"), ("edge", "noise"): ("edge", "satnoise"), ("edge", "vstripe"): ("edge", "ramp")}
 FIXTURE_KEYS = ("payload", "payload_len", "mb_bits", "frame_info")
 

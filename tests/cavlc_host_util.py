@@ -10,7 +10,7 @@ import numpy as np
 from paths import ROOT
 from x264_vs2008_amd.slice import PAYLOAD_LEAD, CavlcParams, MbState
 
-MB_BYTES_MAX = 2624           # CV_MB_BYTES_MAX (csrc/frame_cavlc.hip): the margin of x264hip_cavlc_write_chains
+MB_BYTES_MAX = 2624           # CV_MB_BYTES_MAX (csrc/frame_cavlc.hip): the margin of both entry points, every slice type
 STATE_ARRAYS = ("mb_type", "partition", "sub_partition", "ref", "ref1", "mv", "mv1", "i4mode", "i16mode", "chroma_mode", "qp", "cbp", "t8",
                 "luma", "luma_dc", "chroma_dc", "chroma_ac")
 _lib = []
@@ -44,16 +44,25 @@ def restore_8x8_levels(a, twin):
     return dict(a, luma=luma)
 
 
+def write_state(st, mb_w, mb_h, slice_type, slice_qp, n_ref0=1, inter=0x33, transform8x8=0, cqm_custom=0, cap=None, margin=MB_BYTES_MAX, slots=1, fill=0):
+    """One chain's state arrays ({name: array of mb_w * mb_h macroblocks}, STATE_ARRAYS) through the host writer into slot 0 of a buffer of
+    `slots` slots of cap bytes filled with `fill`.  Returns (0 or the writer's stop count, the whole buffer [slots][cap], payload_len,
+    mb_bits [n_mb])."""
+    st = {k: np.ascontiguousarray(st[k]) for k in STATE_ARRAYS}
+    cap = cap or PAYLOAD_LEAD + MB_BYTES_MAX + mb_w * mb_h * 1200
+    payload, plen, bits = np.full((slots, cap), fill, np.uint8), np.zeros(1, np.int32), np.zeros(mb_w * mb_h, np.int32)
+    state = MbState(**{k: st[k].ctypes.data for k in STATE_ARRAYS})
+    par = CavlcParams(slice_type, n_ref0, inter, transform8x8, cqm_custom, payload.ctypes.data, cap, plen.ctypes.data, bits.ctypes.data, slice_qp)
+    rc = host_writer().cavlc_host_write_slice(C.byref(state), C.byref(par), mb_w, mb_h, margin)
+    return rc, payload, int(plen[0]), bits
+
+
 def write_slice(a, f, p, cap=None):
     """The host writer's bytes for frame f of harness output `a`: its arrays as one chain's x264hip_mb_state, slice type / QP / list-0 size
     from the harness's frame_info, p the rs.Params the arrays were made with."""
-    st = {k: np.ascontiguousarray(a[k][f]) for k in STATE_ARRAYS}
     mb_w, mb_h = (p.width + 15) // 16, (p.height + 15) // 16
-    cap = cap or PAYLOAD_LEAD + MB_BYTES_MAX + mb_w * mb_h * 1200
-    payload, plen = np.zeros(cap, np.uint8), np.zeros(1, np.int32)
-    state = MbState(**{k: st[k].ctypes.data for k in STATE_ARRAYS})
     slice_type, slice_qp, n_ref0 = (int(v) for v in a["frame_info"][f, :3])
-    par = CavlcParams(slice_type, n_ref0, p.inter, p.transform8x8, int(p.cqm_preset != 0), payload.ctypes.data, cap, plen.ctypes.data, None, slice_qp)
-    rc = host_writer().cavlc_host_write_slice(C.byref(state), C.byref(par), mb_w, mb_h, MB_BYTES_MAX)
+    rc, payload, plen, _ = write_state({k: a[k][f] for k in STATE_ARRAYS}, mb_w, mb_h, slice_type, slice_qp, n_ref0, p.inter, p.transform8x8,
+                                       int(p.cqm_preset != 0), cap)
     assert rc == 0, "the host writer stopped (%d) in frame %d" % (rc, f)
-    return bytes(payload[PAYLOAD_LEAD:PAYLOAD_LEAD + int(plen[0])])
+    return bytes(payload[0, PAYLOAD_LEAD:PAYLOAD_LEAD + plen])

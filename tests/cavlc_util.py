@@ -20,6 +20,10 @@ CONFIGS = {
     "aq_intra_qp_clip": dict(w=144, h=112, n=4, ext=dict(aq_mode=1, aq_strength=2.5),
                              kw=dict(qp=47, me_method=rs.ME_HEX, subme=1, n_refs=1, inter=0x11, intra=0x3, transform8x8=1, cabac=0, deblock=1, keyint=2)),
 }
+# tests/edge_cases.py's chains at QP 1 (level codes in the extended escape, both profiles' arms) that tests/test_cavlc_host.py runs through the
+# host-compiled writer: every content at the smallest size, the size with padding in both directions and the largest
+QP1_CONFIGS = ("cavlc_qp1_high", "cavlc_qp1_base")
+QP1_SIZES = ((16, 16), (24, 24), (40, 24))
 
 
 def reference(c, t0=0):

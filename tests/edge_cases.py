@@ -11,7 +11,16 @@ A configuration names where its expected values come from:
   "twin"   x264o_encode_chain2 with the CABAC writer in the loop (pinned to the reference by tests/test_oracle_edge_chains.py),
   "plain"  x264o_encode_chain, no writer: the wavefront variant of the sweep, whose rows wait on each other,
   "ref"    the reference's own loop as recorded in tests/golden/edge_chains.npz (what the twin does not code: CAVLC payloads, lossless
-           above subme 5)."""
+           above subme 5).
+
+Lossy QP 0..7 and escape-range levels are covered by the LOW_QP configurations: QP 1 (cavlc_qp1_high, cavlc_qp1_base, cavlc_b_qp1, s5_qp1,
+rd9_t2_qp1, b_temporal_qp1, plain_s5_qp1), QP 2 under strong adaptive quantisation (cavlc_aq_qp2, rd7_aq_qp2, rd8_b_aq_qp2) and --cqm jvt
+at QP 6 (jvt_qp6), plus the chain table's second QP assignment TABLE_LOW_QPS (1, 2, 3).  Their I slices (iframe_qp(1..3) = 0) and their
+lowest adaptive-quantisation macroblocks are at QP 0 in a chain that is not lossless; levels reach 2967 under CAVLC (level codes >= 4096:
+the High profile's growing prefix in cavlc_qp1_high, the Baseline clamp in cavlc_qp1_base), 3277 and more under CABAC, 3679 with the JVT
+matrices; rd9_t2_qp1 chooses I_PCM at every size.  low_qp_problems() asserts all that, on the reference in the generator and on the twin in
+tests/test_oracle_edge_chains.py; the fixture keeps each such chain's largest |level| (<name>_max_level), which writer_branch() turns into
+the writer branch a failing chain was in."""
 import ctypes as C
 import functools
 import hashlib
@@ -99,6 +108,32 @@ CONFIGS = {
     "ll_rd8": ("ref", dict(qp=0, subme=8, me_method=rs.ME_HEX, n_refs=2, inter=0x13, intra=0x3, transform8x8=1, mixed_refs=1, cabac=1, deblock=1, fast_pskip=0), dict(), 5),
     "ll_rd9": ("ref", dict(qp=0, subme=9, me_method=rs.ME_UMH, n_refs=2, inter=0x13, intra=0x3, transform8x8=1, mixed_refs=1, cabac=1, deblock=1, fast_pskip=0), dict(), 5),
 }
+
+
+def at_qp(name, qp, **ext):
+    """Configuration `name` at another constant QP (ext: what its harness extension takes on top)."""
+    src, kw, ekw, frames = CONFIGS[name]
+    return src, dict(kw, qp=qp), None if ekw is None else dict(ekw, **ext), frames
+
+
+# ---- lossy QP 0..7: levels in the escape range of every entropy writer (CAVLC: level codes >= 4096, the High profile's growing prefix and
+# the Baseline clamp; CABAC: deep in the Exp-Golomb tail of coeff_abs_level_minus1), macroblocks at QP 0 in a slice that is NOT lossless
+# (I slices of QP 1..3 clip to 0, adaptive quantisation at QP 2 reaches it), I_PCM chosen often.  low_qp_problems() states what they reach.
+CAVLC_QP1 = dict(qp=1, me_method=rs.ME_HEX, subme=5, n_refs=2, inter=0x33, intra=0x3, transform8x8=1, mixed_refs=1, cabac=0, deblock=1)
+LOW_QP = {
+    "cavlc_qp1_high": ("ref", CAVLC_QP1, dict(), 5),
+    "cavlc_qp1_base": ("ref", dict(CAVLC_QP1, inter=0x31, intra=0x1, transform8x8=0), dict(), 5),
+    "cavlc_b_qp1": at_qp("cavlc_b", 1),
+    "cavlc_aq_qp2": at_qp("cavlc_aq", 2, aq_strength=1.8),
+    "s5_qp1": at_qp("s5_med", 1),
+    "rd7_aq_qp2": at_qp("rd7_t1_aq", 2, aq_strength=1.8),
+    "rd9_t2_qp1": ("twin", dict(qp=1, subme=9, **MED), dict(trellis=2, psy_rd=0.0), 5),
+    "b_temporal_qp1": at_qp("b_temporal", 1),
+    "rd8_b_aq_qp2": at_qp("rd8_b_aq", 2),
+    "plain_s5_qp1": at_qp("plain_s5", 1),
+    "jvt_qp6": at_qp("jvt", 6),
+}
+CONFIGS.update(LOW_QP)
 TWIN = [k for k, c in CONFIGS.items() if c[0] == "twin"]
 PLAIN = [k for k, c in CONFIGS.items() if c[0] == "plain"]
 REF = [k for k, c in CONFIGS.items() if c[0] == "ref"]
@@ -172,8 +207,12 @@ TABLE_QPS = (8, 26, 51)
 TABLE = {"ch_rd": "rd7_t1_aq", "ch_rf": "rd9", "ll_ch": "lossless", "ll_ch_rf": "ll_rd8"}
 
 
-def table_qps(name):
-    return [0 if CONFIGS[name][1]["qp"] == 0 else TABLE_QPS[b % 3] for b in range(len(CONTENTS))]
+TABLE_LOW_QPS = (1, 2, 3)           # a second assignment for the lossy tables: chains at QP 1, 2 and 3 side by side (tablelow_<name>_*)
+TABLE_LOSSY = [n for n in TABLE.values() if CONFIGS[n][1]["qp"] != 0]
+
+
+def table_qps(name, low=False):
+    return [0 if CONFIGS[name][1]["qp"] == 0 else (TABLE_LOW_QPS if low else TABLE_QPS)[b % 3] for b in range(len(CONTENTS))]
 
 
 def params(name, size, qp=None):
@@ -227,10 +266,36 @@ def fixture():
 
 def recorded(name, size, kind, table=False):
     """(payload md5 [frames][16], mb_type md5 [frames][16], {array: md5}) of the reference's chain as tests/golden/edge_chains.npz holds it.
-    table: the chain at its chain-table QP (table_qps), recorded as table_<name>_* over TABLE_SIZES."""
+    table: the chain at its chain-table QP (table_qps), recorded as table_<name>_* over TABLE_SIZES; table="low": at table_qps(name, low=True),
+    tablelow_<name>_*."""
     g, i, j = fixture(), (TABLE_SIZES if table else SIZES).index(size), CONTENTS.index(kind)
-    name = "table_" + name if table else name
+    name = ("tablelow_" if table == "low" else "table_" if table else "") + name
     return g[name + "_payload"][i, j], g[name + "_mb_type"][i, j], {k: bytes(g[name + "_whole"][i, j, n]) for n, k in enumerate(WHOLE)}
+
+
+LEVELS = ("luma", "luma_dc", "chroma_dc", "chroma_ac")
+
+
+def max_level(a):
+    """The largest |level| among the recorded coefficient levels of one chain."""
+    return max(int(np.abs(a[k].astype(np.int32)).max()) for k in LEVELS)
+
+
+def recorded_max_level(name, size, kind):
+    """The largest |level| of the reference's chain (<name>_max_level of the fixture, the LOW_QP configurations), None where none is kept."""
+    g = fixture()
+    return int(g[name + "_max_level"][SIZES.index(size), CONTENTS.index(kind)]) if name + "_max_level" in g else None
+
+
+def writer_branch(name, size, kind):
+    """For a failure's message: where the chain's largest level puts it in the entropy writers."""
+    m = recorded_max_level(name, size, kind)
+    if m is None:
+        return ""
+    if not CONFIGS[name][1].get("cabac"):
+        arm = "High profile's growing prefix" if CONFIGS[name][1].get("transform8x8") or CONFIGS[name][1].get("cqm_preset") else "Baseline clamp"
+        return " [largest |level| %d: %s]" % (m, "CAVLC level code >= 4096, the " + arm if m >= CAVLC_ESCAPE_LEVEL else "below the CAVLC extended escape")
+    return " [largest |level| %d: %d bits of Exp-Golomb suffix]" % (m, 2 * max(m - 14, 1).bit_length() - 1 if m > 14 else 0)
 
 
 def have_reference():
@@ -239,6 +304,36 @@ def have_reference():
 
 def size_id(s):
     return "%dx%d" % s
+
+
+# |level| from which cv_residual's level code is >= 4096 at every suffix length (the extended escape: 2064 at suffix length 0, 2529 at 6)
+CAVLC_ESCAPE_LEVEL = 2600
+JVT_LEVEL = 3000
+
+
+def low_qp_problems(chains):
+    """What the LOW_QP configurations must reach, over [(configuration, size, content kind, mb_type [frames][n_mb], qp [frames][n_mb],
+    largest |level|)]: a list of what is missing.  The two cavlc_qp1 configurations have, at every size, a chain with a level whose CAVLC
+    code is in the extended escape; every one but jvt_qp6 has a macroblock at QP 0 (none of them is lossless); rd9_t2_qp1 chooses I_PCM
+    at every size; jvt_qp6 reaches |level| >= 3000."""
+    esc, pcm, qp0, top = {}, set(), set(), {}
+    for name, size, kind, t, qp, lvl in chains:
+        if name not in LOW_QP:
+            continue
+        assert CONFIGS[name][1]["qp"] != 0
+        top[name] = max(top.get(name, 0), lvl)
+        if lvl >= CAVLC_ESCAPE_LEVEL:
+            esc.setdefault(name, set()).add(size)
+        if name == "rd9_t2_qp1" and (t == I_PCM).any():
+            pcm.add(size)
+        if (qp == 0).any():
+            qp0.add(name)
+    bad = ["%s: no |level| >= %d at %dx%d" % ((name, CAVLC_ESCAPE_LEVEL) + s) for name in ("cavlc_qp1_high", "cavlc_qp1_base") for s in SIZES if s not in esc.get(name, ())]
+    bad += ["%s: no macroblock at QP 0" % name for name in LOW_QP if name != "jvt_qp6" and name not in qp0]
+    bad += ["rd9_t2_qp1: no I_PCM macroblock at %dx%d" % s for s in SIZES if s not in pcm]
+    if top.get("jvt_qp6", 0) < JVT_LEVEL:
+        bad.append("jvt_qp6: largest |level| %d, below %d" % (top.get("jvt_qp6", 0), JVT_LEVEL))
+    return bad
 
 
 def coverage_problems(chains):

@@ -90,3 +90,14 @@ def test_cases_reach_every_branch(oracle_lib):
             total[k] = total.get(k, 0) + v
     assert len(total) == 24 and all(v > 0 for v in total.values()), "syntax branches the cases never reach: %s" % [k for k, v in total.items() if not v]
     assert sum("aq_mode" in c.get("ext", {}) for c in cc.CASES.values()) == 3
+
+
+def test_qp1_cases_reach_the_exp_golomb_tail(oracle_lib):
+    """The QP 1 cases are there for levels beyond 2900 in a slice that is lossy at QP 0 (an I slice of a QP 1 chain): each size has them."""
+    for size in cc.QP1_SIZES:
+        top, qp0 = 0, False
+        for kind in cc.QP1_KINDS:
+            a = cc.twin_arrays(oracle_lib, cc.CASES["qp1_%dx%d_%s" % (size + (kind,))])
+            top = max(top, max(int(np.abs(a[k].astype(np.int32)).max()) for k in ("luma", "luma_dc", "chroma_dc", "chroma_ac")))
+            qp0 |= bool((a["frame_info"][:, 1] == 0).any())
+        assert top >= cc.QP1_LEVEL and qp0, "%dx%d: largest |level| %d, a slice at QP 0: %s" % (size + (top, qp0))

@@ -79,6 +79,17 @@ def test_pass_equals_in_loop_writer_edge_pictures(hip_lib, size):
     same(ec.size_id(size), run(hip_lib, size, clips, 3, None, MED), run(hip_lib, size, clips, 3, True, MED))
 
 
+@pytest.mark.parametrize("size", cc.QP1_SIZES, ids=ec.size_id)
+def test_pass_equals_in_loop_writer_at_qp1(hip_lib, size):
+    """Lossy QP 1 (the I slice at QP 0, which is not lossless): levels beyond 2900, deep in the Exp-Golomb tail of coeff_abs_level_minus1, in
+    both writers.  The same chains against the reference's bytes: test_pass_equals_reference_fixture's qp1_* cases."""
+    clips = [ec.clip(kind, size, 3) for kind in cc.QP1_KINDS]
+    loop = run(hip_lib, size, clips, 3, None, cc.QP1_KW)
+    top = max(int(np.abs(r[k].astype(np.int32)).max()) for r in loop for k in ("luma", "luma_dc", "chroma_dc", "chroma_ac"))
+    assert top >= cc.QP1_LEVEL, "largest |level| %d" % top
+    same("qp1 " + ec.size_id(size), loop, run(hip_lib, size, clips, 3, True, cc.QP1_KW))
+
+
 def test_pass_equals_in_loop_writer_adaptive_quantisation(hip_lib):
     clips = [rs.clip(96, 80, 4, t0) for t0 in (0, 5)]
     kw, ext = dict(MED, qp=30, n_refs=2), dict(aq_mode=1, aq_strength=1.5)

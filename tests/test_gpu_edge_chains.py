@@ -78,7 +78,7 @@ def test_tiny_picture_chains(hip_lib, oracle_lib, cqm, size, name):
             enc.sync()
             fin = [planes(enc, recon, b) for b in range(B)] if stype != sl.SLICE_B else None
             for b, kind in enumerate(E.CONTENTS):
-                what = "%s %dx%d chain %d (%s) frame %d (%s, display %d)" % (name, size[0], size[1], b, kind, f, "PBI"[stype], disp)
+                what = "%s %dx%d chain %d (%s) frame %d (%s, display %d)%s" % (name, size[0], size[1], b, kind, f, "PBI"[stype], disp, E.writer_branch(name, size, kind))
                 a = want[b]
                 if a is not None:
                     assert (st, qp) == (int(a["frame_info"][f, 0]), int(a["frame_info"][f, 1])), "%s: (slice type, QP) %s" % (what, (st, qp))

@@ -38,15 +38,12 @@ def test_twin_equals_reference_on_tiny_pictures(oracle_lib, size, name):
                 assert bytes(got_whole[i]) == whole[k], "%s: %s differs between the twin and the reference" % (what, k)
 
 
-TABLE_LOSSY = [n for n in E.TABLE.values() if E.CONFIGS[n][1]["qp"] != 0]
+TABLE_LOSSY = E.TABLE_LOSSY
 
 
-@pytest.mark.parametrize("name", TABLE_LOSSY)
-@pytest.mark.parametrize("size", E.TABLE_SIZES, ids=E.size_id)
-def test_twin_equals_reference_at_the_chain_table_qps(oracle_lib, size, name):
-    """tests/test_gpu_edge_table.py expects the twin run at each chain's own QP (8, 26, 51): the twin is the reference there too."""
+def table_chains_equal_reference(size, name, low):
     frames = E.CONFIGS[name][3]
-    for kind, qp in zip(E.CONTENTS, E.table_qps(name)):
+    for kind, qp in zip(E.CONTENTS, E.table_qps(name, low)):
         what = "%s %dx%d %s at QP %d" % (name, size[0], size[1], kind, qp)
         a = E.twin_chain(name, size, kind, qp)
         if E.have_reference():
@@ -56,12 +53,44 @@ def test_twin_equals_reference_at_the_chain_table_qps(oracle_lib, size, name):
             for k in E.DECISIONS + E.PLANES:
                 assert np.array_equal(a[k], b[k]), "%s: %s" % (what, k)
         else:
-            pay, mbt, whole = E.recorded(name, size, kind, table=True)
+            pay, mbt, whole = E.recorded(name, size, kind, table="low" if low else True)
             got_pay, got_mbt, got_whole = E.digests(a, name)
             assert np.array_equal(got_pay, pay), "%s: payloads differ between the twin and the reference" % what
             assert np.array_equal(got_mbt, mbt), "%s: mb_type differs between the twin and the reference" % what
             for i, k in enumerate(E.WHOLE):
                 assert bytes(got_whole[i]) == whole[k], "%s: %s differs between the twin and the reference" % (what, k)
+
+
+@pytest.mark.parametrize("name", TABLE_LOSSY)
+@pytest.mark.parametrize("size", E.TABLE_SIZES, ids=E.size_id)
+def test_twin_equals_reference_at_the_chain_table_qps(oracle_lib, size, name):
+    """tests/test_gpu_edge_table.py expects the twin run at each chain's own QP (8, 26, 51): the twin is the reference there too."""
+    table_chains_equal_reference(size, name, False)
+
+
+@pytest.mark.parametrize("name", TABLE_LOSSY)
+@pytest.mark.parametrize("size", E.TABLE_SIZES, ids=E.size_id)
+def test_twin_equals_reference_at_the_low_chain_table_qps(oracle_lib, size, name):
+    """... and at the second assignment, QP 1, 2 and 3 side by side."""
+    table_chains_equal_reference(size, name, True)
+
+
+def test_low_qp_configurations_reach_the_escapes_qp0_and_ipcm(oracle_lib):
+    """What the LOW_QP configurations are there for (edge_cases.low_qp_problems), on the twin's arrays; and the largest |level| of every
+    chain is the one recorded from the reference (a CAVLC chain with the 8x8 transform: at least that, the reference's harness records such
+    levels incompletely)."""
+    chains = []
+    for name in E.LOW_QP:
+        for size in E.SIZES:
+            for kind in E.CONTENTS:
+                a = E.twin_chain(name, size, kind)
+                chains.append((name, size, kind, a["mb_type"], a["qp"], E.max_level(a)))
+                want, kw = E.recorded_max_level(name, size, kind), E.CONFIGS[name][1]
+                lower_bound = not kw.get("cabac") and kw.get("transform8x8")
+                assert chains[-1][5] >= want if lower_bound else chains[-1][5] == want, "%s %dx%d %s: largest |level| %d, the reference's %d" % (
+                    (name,) + size + (kind, chains[-1][5], want))
+    bad = E.low_qp_problems(chains)
+    assert not bad, "the low-QP configurations lost what they are there for:\n  " + "\n  ".join(bad)
 
 
 def test_case_list_reaches_every_macroblock_type_and_kernel_kind(oracle_lib):

@@ -21,8 +21,9 @@
 
 using namespace x264hip;
 
-// The worst case of one CAVLC macroblock, for the "slot too small" check of x264hip_cavlc_write_chains and of B slices: the writer
-// stops BEFORE a macroblock that might not fit.  Bits, every syntax element at the longest code its type can take in this writer:
+// The worst case of one CAVLC macroblock, for the "slot too small" check of both entry points and every slice type: the writer checks
+// for space at the START of a macroblock only and stops BEFORE one that might not fit, so nothing smaller than this may be kept free.
+// Bits, every syntax element at the longest code its type can take in this writer:
 //   mb_skip_run          ue(v) of a 32-bit count                                                        63
 //   mb_type              ue(v <= 48)                                                                    11
 //   prediction           the larger of: I_4x4 (1 + 16 x 4 + ue(3) = 70) and P_8x8 with sub-8x8
@@ -35,8 +36,12 @@ using namespace x264hip;
 //                        17 x 769 + 2 x 158 + 8 x 769                                                                19541
 // 63 + 11 + 1112 + 23 + 19541 = 20750 bits = 2594 bytes; the slice's end (the last skip run and the trailing bits, 63 + 8 bits) and the
 // 7 bits cv_put may hold back add 10: 2604, rounded up to the next multiple of 64.
+// Measured (tests/test_cavlc_host.py on tests/cavlc_synth.py's hand-built 3x2 slices, every level -32768 or +-32767 in turn, the largest
+// macroblock of each in bits, High / Baseline profile): all I_16x16 14049 / 10977, all I_4x4 14091 / 11018, all P_8x8 of 4x4 blocks on
+// reference 15 of 16 with vector differences of +-65535 15138 / 12066, all B_8x8 of bi-predicted blocks 14615 / 11542 -- at most 1893
+// bytes.  The sum above is not reachable as a whole: 16 non-zero levels leave no total_zeros or run_before (- 174 bits a block), a block of 15
+// coefficients holds 15 levels, and no macroblock type has both the 17 luma blocks and the P_8x8 prediction.
 #define CV_MB_BYTES_MAX 2624
-#define CV_MARGIN_FRAME 1024           // x264hip_cavlc_write_frame's I and P slices: as before (payload_cap >= 4096 is its precondition)
 
 // every chain's slice of one frame: the same arguments, the chain is the block
 __global__ __launch_bounds__(64) void k_cavlc_write(CvArgs a)
@@ -69,8 +74,8 @@ extern "C" int x264hip_cavlc_write_frame(x264hip_frame_ctx *c, const x264hip_mb_
 {
     CvArgs a;
     if (cv_build(c, st, p, "cavlc_write_frame", a)) return -1;
+    static_assert(4096 >= X264HIP_PAYLOAD_LEAD + CV_MB_BYTES_MAX, "the precondition implies room for one macroblock's worst case");
     if (p->payload_cap < 4096) { set_error("cavlc_write_frame: payload_cap"); return -1; }
-    if (p->slice_type != 1) a.margin = CV_MARGIN_FRAME;                        // I and P slices here: as before
     hipLaunchKernelGGL(k_cavlc_write, dim3((unsigned)c->batch), dim3(64), 0, c->stream, a);
     HIPCHK(hipGetLastError());
     return 0;
