@@ -291,8 +291,8 @@ typedef struct {
  * wavefront owns a whole frame of one chain of the batch and walks it in raster order, and the entropy coder runs inside the
  * loop exactly where x264_slice_write has it (R/encoder/encoder.c:1155-1165,1192-1205,1269-1273): the launch also returns every
  * chain's slice_data() bytes.  Throughput then comes from the number of chains in flight (the batch), not from a wavefront
- * schedule inside the frame.  I, P and B slices, CABAC; refused with an error string: sub-8x8 partitions together with the RD levels,
- * subme 9 in B slices, CAVLC together with the writer; psy-trellis without trellis, at QP 0 or without psy_carry.        */
+ * schedule inside the frame.  I, P and B slices, CABAC; refused with an error string: sub-8x8 partitions together with the RD levels
+ * without mb_carry, in B slices or at QP 0, subme 9 in B slices, CAVLC together with the writer; psy-trellis without trellis, at QP 0 or without psy_carry.        */
 typedef struct x264hip_slice_rd {
     int trellis;                   /* param.analyse.i_trellis 0..2 */
     int psy_rd;                    /* h->mb.i_psy_rd = FIX8(param.analyse.f_psy_rd) (0 below subme 6); the caller lowers chroma_qp_offset
@@ -330,6 +330,15 @@ typedef struct x264hip_slice_rd {
                                       size h->mb.b_transform_8x8 names after the analysis, R/encoder/analyse.c:2770-2771; trellis 2: only with the RD
                                       levels, :515-516), so a block may be priced against what an earlier macroblock or frame left.  Every sweep of
                                       a chain reads and updates its slot */
+    uint8_t *mb_carry;             /* device [batch] records of 160 bytes (zero before a chain's first frame; never reset between frames), or NULL:
+                                      h->mb.cache.non_zero_count and h->mb.cache.mvd at the macroblock's OWN blocks -- 27 counts (16 luma, 4 U, 4 V,
+                                      luma DC, U DC, V DC) padded to 32 bytes, then int16 mvd[2][16][2] (list 0, then list 1; the 16 blocks in
+                                      raster order).  x264_macroblock_cache_load rewrites the neighbours' entries only, and a partial trial encode
+                                      that runs before any full one (x264_mb_analyse_p_rd with X264_ANALYSE_PSUB8x8, R/encoder/analyse.c:1966-1996
+                                      and its FIXME) prices against what the previous macroblock -- at a frame's start, the previous frame -- left.
+                                      Required by sub-8x8 partitions (analyse_inter & 0x20) with the RD levels (subme 6-9); hand it to EVERY sweep
+                                      of the chain in coding order, I and P alike, given-up attempts included.  Without it that combination is
+                                      refused.  Not built: a B slice of such a chain, lossless.  A chain table has it in every entry or in none */
 } x264hip_slice_rd;
 #define X264HIP_PAYLOAD_LEAD 64
 

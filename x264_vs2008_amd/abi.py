@@ -69,7 +69,8 @@ class SliceRd(C.Structure):
     _fields_ = [("trellis", C.c_int), ("psy_rd", C.c_int), ("write", C.c_int), ("cabac_init_idc", C.c_int), ("i_frame", C.c_int),
                 ("qp_min", C.c_int), ("qp_max", C.c_int), ("f_qpm", C.c_float), ("aq_offset", C.c_void_p), ("cost_mv_all", C.c_void_p),
                 ("unquant4_mf", C.c_void_p), ("unquant8_mf", C.c_void_p), ("payload", C.c_void_p), ("payload_cap", C.c_int),
-                ("payload_len", C.c_void_p), ("mb_bits", C.c_void_p), ("stale", C.c_void_p), ("i_frame_stride", C.c_int), ("psy_trellis", C.c_int), ("psy_carry", C.c_void_p)]
+                ("payload_len", C.c_void_p), ("mb_bits", C.c_void_p), ("stale", C.c_void_p), ("i_frame_stride", C.c_int), ("psy_trellis", C.c_int), ("psy_carry", C.c_void_p),
+                ("mb_carry", C.c_void_p)]
 
 
 class SliceParams(C.Structure):

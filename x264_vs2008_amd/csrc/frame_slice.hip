@@ -184,7 +184,13 @@ static int sweep_build(x264hip_frame_ctx *c, const x264hip_picture *fenc, const 
         // with trellis 1 always; with trellis 2 a B slice below the RD levels reads, and an I or P slice at subme 6 writes (slice_sweep_body.h)
         if (prd->psy_trellis && !prd->psy_carry && (prd->trellis == 1 || (is_b ? !mbrd : (mbrd && p->subme == 6)))) { set_error("slice_sweep: psy-trellis needs x264hip_slice_rd.psy_carry (in every sweep of the chain)"); return -1; }
         if (p->lossless && prd->aq_offset) { set_error("slice_sweep: lossless with adaptive quantisation (constant QP 0 has no AQ: every macroblock is coded at QP 0)"); return -1; }
-        if (mbrd && (p->analyse_inter & 0x20)) { set_error("slice_sweep: sub-8x8 partitions with the RD levels not built (their partial bit counts read cache entries the previous macroblock left)"); return -1; }
+        // sub-8x8 partitions with the RD levels: the partial bit counts of x264_mb_analyse_p_rd read cache entries the previous macroblock (of this
+        // frame or of the one before) left, so the chain carries them (x264hip_slice_rd.mb_carry) through every sweep.  I and P slices, in the
+        // refinement kernels; the B kernels do not keep the reference's leftovers, so a B slice of such a chain is refused
+        if (mbrd && (p->analyse_inter & 0x20) && !prd->mb_carry) { set_error("slice_sweep: sub-8x8 partitions with the RD levels need x264hip_slice_rd.mb_carry (in every sweep of the chain): their partial bit counts read cache entries the previous macroblock left"); return -1; }
+        if (mbrd && (p->analyse_inter & 0x20) && p->lossless) { set_error("slice_sweep: lossless with sub-8x8 partitions and the RD levels is not built"); return -1; }
+        // (a chain whose I / P slices never read the record -- no sub-8x8 partitions, or below the RD levels -- may hand it to its B slices too: nobody uses it)
+        if (is_b && prd->mb_carry && (p->analyse_inter & 0x20) && p->subme >= 6) { set_error("slice_sweep: a B slice in a chain with x264hip_slice_rd.mb_carry (sub-8x8 partitions with the RD levels) is not built: the B kernels do not keep the cache entries a macroblock leaves behind"); return -1; }
         if (!out->mvd) { set_error("slice_sweep: mb_state without mvd"); return -1; }
     }
     if (!out->luma && !(prd && prd->write)) { set_error("slice_sweep: an mb_state without level arrays (X264HIP_STATE_NO_LEVELS) needs the entropy coder in the loop (rd.write)"); return -1; }
@@ -286,6 +292,7 @@ static int sweep_build(x264hip_frame_ctx *c, const x264hip_picture *fenc, const 
         r.payload = prd->payload; r.payload_cap = prd->payload_cap; r.payload_len = prd->payload_len; r.mb_bits = prd->mb_bits;
         r.mvd = out->mvd;
         r.stale = prd->stale;
+        if (!is_b) r.mb_carry = prd->mb_carry;                       // (shares its place with skipbp, which only a B slice has)
         if (is_b) {
             r.direct_temporal = !pb->direct_spatial;
             r.direct_score = pb->direct_score;
@@ -293,7 +300,10 @@ static int sweep_build(x264hip_frame_ctx *c, const x264hip_picture *fenc, const 
             r.col_type = (const signed char *)pb->l1_state->mb_type; r.col_ref = (const signed char *)pb->l1_state->ref; r.col_mv = pb->l1_state->mv;
         }
     }
-    kind = sweep_kind(prd != nullptr, is_b, a.lossless, mbrd, r.psy_trellis != 0, r.direct_temporal || r.direct_score || a.lowres0 || a.lowres1);
+    // sub-8x8 partitions with the RD levels are coded by the refinement kinds, whatever the level: those kernels gate the refinement itself on
+    // the real mbrd at run time, and the subme 6-7 kernels stay the ones they were
+    const bool sub8_rd = prd && !is_b && mbrd && (p->analyse_inter & 0x20);
+    kind = sweep_kind(prd != nullptr, is_b, a.lossless, sub8_rd ? 2 : mbrd, r.psy_trellis != 0, r.direct_temporal || r.direct_score || a.lowres0 || a.lowres1);
     return 0;
 }
 
@@ -384,7 +394,7 @@ static int sweep_chains(x264hip_frame_ctx *c, x264hip_chain_sweep *e, int n, voi
     if (!staging_host || !table_dev) { set_error("slice_sweep_chains: staging / table buffers missing"); return -1; }
     SwDesc *st = (SwDesc *)staging_host;
     // entries sorted by kind (sweep_tables.h): a first pass builds, a second places
-    int cnt[SW_N_KINDS] = {0}, n_cavlc = 0;
+    int cnt[SW_N_KINDS] = {0}, n_cavlc = 0, n_carry = 0;
     static thread_local std::vector<SwDesc> tmp;
     static thread_local std::vector<int> kinds;
     tmp.resize((size_t)n); kinds.resize((size_t)n);
@@ -393,6 +403,7 @@ static int sweep_chains(x264hip_frame_ctx *c, x264hip_chain_sweep *e, int n, voi
         if (s.chain < 0 || s.chain >= c->batch) { set_error("slice_sweep_chains: entry %d: chain %d", i, s.chain); return -1; }
         if (!s.params || !s.params->rd || (!s.params->rd->write && s.params->cabac)) { set_error("slice_sweep_chains: entry %d: the chain table belongs to the raster variant (params.rd) with the CABAC coder in the loop (write = 1), or without a writer for a CAVLC slice (cabac = 0, write = 0)", i); return -1; }
         n_cavlc += !s.params->rd->write;
+        n_carry += s.params->rd->mb_carry != nullptr;
         int kind;
         if (sweep_build(c, s.fenc, s.refs, s.n_refs, s.recon, s.params, s.l0, s.out, tmp[i].a, tmp[i].t, tmp[i].r, kind)) return -1;
         kind = k_sweep_kinds[kind].in_table;
@@ -408,6 +419,8 @@ static int sweep_chains(x264hip_frame_ctx *c, x264hip_chain_sweep *e, int n, voi
     // ... and all-CAVLC or not at all: the caller follows the launch with ONE x264hip_cavlc_write_chains over the same chains, and a CABAC
     // chain's payload slot already holds its slice then
     if (n_cavlc && n_cavlc != n) { set_error("slice_sweep_chains: %d of %d entries are CAVLC slices without a writer (cabac = 0, rd.write = 0): a chain table is all-CAVLC or not at all", n_cavlc, n); return -1; }
+    // ... and with x264hip_slice_rd.mb_carry in every entry or in none: sub-8x8 partitions under the RD levels are a setting of the whole encode
+    if (n_carry && n_carry != n) { set_error("slice_sweep_chains: %d of %d entries have x264hip_slice_rd.mb_carry: a chain table carries the macroblock cache's leftovers in every entry or in none", n_carry, n); return -1; }
     // ... and all-psy-trellis or not at all: its kernels are others (k_psy_raster), one launch per kind, and the strength is a setting of the whole encode
     if (mixed == SW_PSY) { set_error("slice_sweep_chains: %d of %d entries have psy-trellis on: a chain table is all-psy-trellis or not at all", n_mixed, n); return -1; }
     int base[SW_N_KINDS], at[SW_N_KINDS];

@@ -171,7 +171,11 @@ struct SwRd {                       // kernel argument
     // B slices: list 1 of the per-macroblock state, h->mb.skipbp, and the co-located picture's arrays (direct prediction)
     i16 *mv1, *mvr1, *mvd1;
     signed char *ref1;
-    u8 *skipbp;
+    union {
+        u8 *skipbp;                 // a B slice: h->mb.skipbp
+        u8 *mb_carry;               // an I / P slice (no list 1, no skip flags: the member is free there, and SwRd keeps its size and every kernel its
+                                    // argument layout): x264hip_slice_rd.mb_carry, [batch][160], the macroblock's own non_zero_count / mvd cache entries
+    };
     const signed char *col_type, *col_ref;
     const i16 *col_mv;
     int direct_temporal;            // !sh.b_direct_spatial_mv_pred
@@ -595,10 +599,10 @@ __device__ __forceinline__ int sw_denoise(int v, int off, int &la)
 // mask8: the 8x8 blocks to do (x264_macroblock_encode_p8x8 codes one); lanes of other blocks leave everything of theirs alone
 template <class TQ>
 __device__ __forceinline__ void sw_luma4x4_fwd(SwLds &s, const SwArgs &a, const SwQp &Q, TQ tq, int cat, bool dc_out, int lane, int *nr_acc4 = nullptr, int nr_on = 0,
-                                               int mask8 = 0xf)
-{
+                                               int mask8 = 0xf, int mask16 = 0xffff)
+{   // mask16: the 4x4 blocks to do among those of mask8 (x264_macroblock_encode_p4x4 codes one)
     i16 c[16], lv[16];
-    const bool mine = lane < 16 && ((mask8 >> (lane >> 2)) & 1);
+    const bool mine = lane < 16 && ((mask8 >> (lane >> 2)) & 1) && (mask16 == 0xffff || ((mask16 >> lane) & 1));
     if (mine) {
         int bx, by, r[16];
         sw_blk_xy(lane, bx, by);
@@ -633,10 +637,10 @@ __device__ __forceinline__ void sw_luma4x4_fwd(SwLds &s, const SwArgs &a, const 
             if ((mask8 >> it) & 1) {
             if constexpr (TQ::PSY) {
                 sw_psy_src4(s, tq, 4 * it + (lane >> 4), lane);
-                td_trellis_wave(tq.r->tw, (u32 *)s.patch, &s.coef[4 * it + (lane >> 4)][0], true, s.qmf[cat], tq.r->unq4[cat], tq.r->w4z, tq.r->zz4, tq.r->cabac, dc_out ? 1 : 2,
+                td_trellis_wave(tq.r->tw, (u32 *)s.patch, &s.coef[4 * it + (lane >> 4)][0], mask16 == 0xffff || ((mask16 >> (4 * it + (lane >> 4))) & 1), s.qmf[cat], tq.r->unq4[cat], tq.r->w4z, tq.r->zz4, tq.r->cabac, dc_out ? 1 : 2,
                                 d_trellis_lambda2[cat == 0][Q.qp], dc_out ? 1 : 0, 0, 16, lane, SW_PSY_FENC(s) + (lane & 48), SwPw4(), tq.psy);
             } else
-            td_trellis_wave(tq.r->tw, (u32 *)s.patch, &s.coef[4 * it + (lane >> 4)][0], true, s.qmf[cat], tq.r->unq4[cat], tq.r->w4z, tq.r->zz4, tq.r->cabac, dc_out ? 1 : 2,
+            td_trellis_wave(tq.r->tw, (u32 *)s.patch, &s.coef[4 * it + (lane >> 4)][0], mask16 == 0xffff || ((mask16 >> (4 * it + (lane >> 4))) & 1), s.qmf[cat], tq.r->unq4[cat], tq.r->w4z, tq.r->zz4, tq.r->cabac, dc_out ? 1 : 2,
                             d_trellis_lambda2[cat == 0][Q.qp], dc_out ? 1 : 0, 0, 16, lane);
             }
         WAVE_SYNC();
@@ -661,9 +665,9 @@ __device__ __forceinline__ void sw_luma4x4_fwd(SwLds &s, const SwArgs &a, const 
     }
     WAVE_SYNC();
 }
-__device__ __forceinline__ void sw_luma4x4_add(SwLds &s, int lane, int keep8)
+__device__ __forceinline__ void sw_luma4x4_add(SwLds &s, int lane, int keep8, int keep16 = 0xffff)
 {
-    if (lane < 16 && ((keep8 >> (lane >> 2)) & 1)) {
+    if (lane < 16 && ((keep8 >> (lane >> 2)) & 1) && (keep16 == 0xffff || ((keep16 >> lane) & 1))) {
         int bx, by, res[16];
         sw_blk_xy(lane, bx, by);
         inv4x4(res, s.coef[lane]);

@@ -6,8 +6,13 @@
 //   x264_macroblock_encode_p8x8     R/encoder/macroblock.c:917-1042
 // A trial that prices the WHOLE macroblock (a 16x16 vector, an I_16x16 mode: x264_rd_cost_mb) leaves this block with rf_emit set and
 // runs through the loop's one tail (encoder, distortion, bit counter); the loop comes back here with its cost.  Everything else
-// -- the partial encodes -- is priced in place.  Sub-8x8 partitions stay refused with the RD levels: the reference's partial bit
-// counts then read cache entries the PREVIOUS macroblock left (oracle/slice_oracle.c: carry_nnz), state this kernel does not carry.
+// -- the partial encodes -- is priced in place.  With sub-8x8 partitions (X264_ANALYSE_PSUB8x8; SUB8, the lossy kernels) the same partial
+// encode also chooses every 8x8 block's sub-partition for step 5 of the candidate loop (rf_kind 4: the sub-8x8 branch of
+// x264_mb_analyse_p_rd, analyse.c:1966-1996, at subme 6-9), and the 8x4 / 4x8 / 4x4 records of a P_8x8 winner are refined through
+//   x264_rd_cost_subpart            R/encoder/rdo.c:175-200
+//   x264_macroblock_encode_p4x4     R/encoder/macroblock.c:1047-1077
+// The reference's partial bit counts then read cache entries the PREVIOUS macroblock left (oracle/slice_oracle.c: carry_nnz / carry_mvd):
+// s.nnz and the own entries of sr.cmvd are never reset, and x264hip_slice_rd.mb_carry takes them from frame to frame (slice_sweep_body.h).
 {
     bool rf_emit = false;
     // ---- the bit counters of the partial costs: lane 0 on a copy of the live contexts (COPY_CABAC, rdo.c:62) ----
@@ -20,6 +25,7 @@
             DCabac tcb = {0, 0x1FE, -1, 0, nullptr, 0};
             MbSynDev y = y0;
             if (kind == 0) cw_partition_size(tcb, sr.cabac_tmp, y, p0, p1);
+            else if (SUB8 && kind == 1) cw_subpartition_size(tcb, sr.cabac_tmp, y, p0, p1);
             else if (kind == 2) cw_partition_i8x8_size(tcb, sr.cabac_tmp, y, p0, p1);
             else if (kind == 3) cw_partition_i4x4_size(tcb, sr.cabac_tmp, y, p0, p1);
             else cw_i8x8_chroma_size(tcb, sr.cabac_tmp, y);
@@ -189,15 +195,27 @@
                 }
             }
             rf_kind = 9;
-        } else if (rf_kind == 3) {
-            // ---- x264_me_refine_qpel_rd on every partition of the winner, analyse.c:2412-2462 ----
+        } else if (rf_kind == 3 || (SUB8 && rf_kind == 4)) {
+            // ---- x264_me_refine_qpel_rd on every partition of the winner, analyse.c:2412-2462 (rf_kind 3), and the choice of every 8x8 block's
+            // sub-partition in x264_mb_analyse_p_rd, :1966-1996 (rf_kind 4, from step 5 of the candidate loop): one copy of x264_rd_cost_part ----
             const int rf_np = part == D_16x16 ? 1 : part == D_8x8 ? 4 : 2;
             if (q_st == -1) {
                 // the references of the partitions into the motion cache (x264_macroblock_cache_ref; a P_8x8 macroblock: x264_analyse_update_cache)
                 if (part == D_16x16) cache_set(0, 0, 4, 4, me16r, 0, 0, 0);
                 else if (part == D_16x8) { cache_set(0, 0, 4, 2, pme(4, 4), 0, 0, 0); cache_set(0, 2, 4, 2, pme(5, 4), 0, 0, 0); }
                 else if (part == D_8x16) { cache_set(0, 0, 2, 4, pme(6, 4), 0, 0, 0); cache_set(2, 0, 2, 4, pme(7, 4), 0, 0, 0); }
-                else for (int i = 0; i < 4; i++) cache_set(2 * (i & 1), 2 * (i >> 1), 2, 2, pme(i, 4), pme(i, 0), pme(i, 1), 1);
+                else for (int i = 0; i < 4; i++) {
+                    cache_set(2 * (i & 1), 2 * (i >> 1), 2, 2, pme(i, 4), pme(i, 0), pme(i, 1), 1);
+                    if constexpr (SUB8) {                            // x264_mb_cache_mv_p8x8 of a block with sub-partitions
+                        const int st = __builtin_amdgcn_readlane(sub_t, i);
+                        if (st != D_L0_8x8) {
+                            const int sn = st == D_L0_4x4 ? 4 : 2, rec0 = st == D_L0_4x4 ? 4 * i : st == D_L0_8x4 ? 16 + 2 * i : 24 + 2 * i;
+                            for (int k = 0; k < sn; k++)
+                                cache_set(2 * (i & 1) + (st == D_L0_4x4 ? (k & 1) : st == D_L0_4x8 ? k : 0), 2 * (i >> 1) + (st == D_L0_4x4 ? (k >> 1) : st == D_L0_8x4 ? k : 0),
+                                          st == D_L0_8x4 ? 2 : 1, st == D_L0_4x8 ? 2 : 1, pme(i, 4), __builtin_amdgcn_readlane(sub_mx, rec0 + k), __builtin_amdgcn_readlane(sub_my, rec0 + k), 1);
+                        }
+                    }
+                }
                 update_cache_p();
                 q_st = 0;
             }
@@ -224,6 +242,34 @@
                 }
             };
             bool have = false;                                       // a candidate (q_cx, q_cy, q_tag) is to be priced
+            if constexpr (SUB8) {
+                // rf_kind 4: block rf_i tries the sub-types q_j = D_L0_4x4, 8x4, 4x8, 8x8 whose SATD cost is within 5/4 of the block's minimum (8x8 only
+                // if one was tried before it); rf_best / q_dir: the best cost and type so far, a later type wins on strict improvement
+                while (!have && rf_kind == 4) {
+                    if (q_st == 0) {
+                        const int c0 = __builtin_amdgcn_readlane(sub_cst, 4 * rf_i), c1 = __builtin_amdgcn_readlane(sub_cst, 4 * rf_i + 1);
+                        const int c2 = __builtin_amdgcn_readlane(sub_cst, 4 * rf_i + 2), c3 = pme(rf_i, 2);
+                        rf_thr = min(min(c0, c1), min(c2, c3)) * 5 / 4;
+                        rf_best = 1ull << 60; q_dir = D_L0_8x8; q_j = 0; q_st = 1;
+                    } else {
+                        while (q_j < 4) {
+                            const int cst = q_j < 3 ? __builtin_amdgcn_readlane(sub_cst, 4 * rf_i + q_j) : pme(rf_i, 2);
+                            if (!(cst > rf_thr || (q_j == 3 && rf_best == 1ull << 60))) break;
+                            q_j++;
+                        }
+                        if (lane == rf_i) sub_t = q_j < 4 ? q_j : q_dir;      // h->mb.i_sub_partition[i] = subtype, or btype once every type is through
+                        sub_t_mb = sub_t;
+                        if (q_j < 4) {
+                            q_pix = 3; q_w = 8; q_h = 8; q_bx = 8 * (rf_i & 1); q_by = 8 * (rf_i >> 1); q_i4 = 4 * rf_i; q_slot = rf_i;
+                            have = true;
+                        } else {
+                            update_cache_p();                        // x264_mb_cache_mv_p8x8 of the winner
+                            rf_i++; q_st = 0;
+                            if (rf_i == 4) { rf_sub = 1; rf_kind = 0; step = 4; }      // back to step 5: the full x264_rd_cost_mb of the P_8x8 candidate
+                        }
+                    }
+                }
+            }
             while (!have && rf_kind == 3) {
                 if (q_st == 0) {                                     // a partition starts: COST_MV_SATD( bmx, bmy, bsatd, 0 ); COST_MV_RD( bmx, bmy, 0, 0, 0 )
                     q_slot = part == D_8x8 ? rf_i : part == D_16x8 ? 4 + rf_i : part == D_8x16 ? 6 + rf_i : -1;
@@ -231,6 +277,17 @@
                     q_w = part == D_16x16 || part == D_16x8 ? 16 : 8; q_h = part == D_16x16 || part == D_8x16 ? 16 : 8;
                     q_bx = part == D_8x8 ? 8 * (rf_i & 1) : part == D_8x16 ? 8 * rf_i : 0; q_by = part == D_8x8 ? 8 * (rf_i >> 1) : part == D_16x8 ? 8 * rf_i : 0;
                     q_i4 = part == D_8x8 ? 4 * rf_i : part == D_16x8 ? 8 * rf_i : part == D_8x16 ? 4 * rf_i : 0;
+                    int q_sub = D_L0_8x8;                            // (SUB8) the block's sub-partition type: its records are refined one by one (analyse.c:2440-2462)
+                    if constexpr (SUB8) { if (part == D_8x8) q_sub = __builtin_amdgcn_readlane(sub_t, rf_i); }
+                    if (q_sub != D_L0_8x8) {
+                        const int rec = (q_sub == D_L0_4x4 ? 4 * rf_i : q_sub == D_L0_8x4 ? 16 + 2 * rf_i : 24 + 2 * rf_i) + rf_k;
+                        q_slot = 16 + rec; q_pix = q_sub == D_L0_4x4 ? 6 : q_sub == D_L0_8x4 ? 4 : 5;
+                        q_w = q_sub == D_L0_8x4 ? 8 : 4; q_h = q_sub == D_L0_4x8 ? 8 : 4;
+                        q_bx += 4 * (q_sub == D_L0_4x4 ? (rf_k & 1) : q_sub == D_L0_4x8 ? rf_k : 0); q_by += 4 * (q_sub == D_L0_4x4 ? (rf_k >> 1) : q_sub == D_L0_8x4 ? rf_k : 0);
+                        q_i4 += q_sub == D_L0_8x4 ? 2 * rf_k : rf_k;
+                        q_bmx = __builtin_amdgcn_readlane(sub_mx, rec); q_bmy = __builtin_amdgcn_readlane(sub_my, rec); q_ref = pme(rf_i, 4);
+                        q_mvpx = __builtin_amdgcn_readlane(sub_px, rec); q_mvpy = __builtin_amdgcn_readlane(sub_py, rec); rf_best = ~0ull >> 4;
+                    } else
                     if (q_slot < 0) { q_bmx = me16x; q_bmy = me16y; q_ref = me16r; q_mvpx = bmvpx; q_mvpy = bmvpy; rf_best = (unsigned long long)(u32)rd16; }
                     else { q_bmx = pme(q_slot, 0); q_bmy = pme(q_slot, 1); q_ref = pme(q_slot, 4); q_mvpx = pme(q_slot, 6); q_mvpy = pme(q_slot, 7); rf_best = ~0ull >> 4; }
                     if (q_pix != 0 && q_i4 != 0) predict_blk(part, q_i4, q_w >> 2, q_mvpx, q_mvpy);
@@ -283,6 +340,7 @@
                 } else {                                             // the partition is done (me.c:1041-1046)
                     q_bmy = clip3(q_bmy, L.smin1, L.smax1);
                     if (q_slot < 0) { me16x = q_bmx; me16y = q_bmy; }
+                    else if (SUB8 && q_slot >= 16) { if (lane == q_slot - 16) { sub_mx = q_bmx; sub_my = q_bmy; } }
                     else { if (lane == q_slot * 8) pme_v = q_bmx; if (lane == q_slot * 8 + 1) pme_v = q_bmy; }
                     cache_set(q_bx >> 2, q_by >> 2, q_w >> 2, q_h >> 2, q_ref, q_bmx, q_bmy, 1);
                     update_cache_p();
@@ -294,17 +352,75 @@
                         }
                     }
                     WAVE_SYNC();
-                    rf_i++; q_st = 0;
+                    if (SUB8 && q_pix >= 4 && rf_k + 1 < (q_pix == 6 ? 4 : 2)) rf_k++;      // the 8x8 block's next sub-block
+                    else { rf_k = 0; rf_i++; }
+                    q_st = 0;
                     if (rf_i >= rf_np) rf_kind = 9;
                 }
             }
             if (have) {
                 // the candidate into the record the encoders read (the cache's two entries of me.c:953-954: here the whole partition, which
                 // nothing else reads while it is being tried)
-                if (q_slot < 0) { me16x = q_cx; me16y = q_cy; rf_emit = true; break; }     // x264_rd_cost_part( .., PIXEL_16x16 ) = x264_rd_cost_mb: the loop's tail
-                if (lane == q_slot * 8) pme_v = q_cx;
-                if (lane == q_slot * 8 + 1) pme_v = q_cy;
-                update_cache_p();
+                if (SUB8 && rf_kind == 4) update_cache_p();          // (the sub-type on trial is in sub_t already)
+                else {
+                    if (q_slot < 0) { me16x = q_cx; me16y = q_cy; rf_emit = true; break; }     // x264_rd_cost_part( .., PIXEL_16x16 ) = x264_rd_cost_mb: the loop's tail
+                    if (SUB8 && q_slot >= 16) { if (lane == q_slot - 16) { sub_mx = q_cx; sub_my = q_cy; } }
+                    else {
+                        if (lane == q_slot * 8) pme_v = q_cx;
+                        if (lane == q_slot * 8 + 1) pme_v = q_cy;
+                    }
+                    update_cache_p();
+                }
+                unsigned long long c64;
+                if (SUB8 && q_pix >= 4) {
+                    // ---- x264_rd_cost_subpart, rdo.c:175-200: x264_macroblock_encode_p4x4 (macroblock.c:1047-1077: luma only, the 4x4 transform, no
+                    // decimation) of the sub-block's one or two 4x4 blocks, their distortion, x264_subpartition_size_cabac ----
+                    const int i4b = q_i4 + (q_pix == 4 ? 1 : 2), two = q_pix != 6, m16 = (1 << q_i4) | (two ? 1 << i4b : 0);
+                    {
+                        const int lox = 4 * (-16 * mbx - 24), hix = 4 * (16 * (a.mb_w - mbx - 1) + 24), loy = 4 * (-16 * mby - 24), hiy = 4 * (16 * (a.mb_h - mby - 1) + 24);
+                        const int ri = UNI((int)s.ref8[q_i4 >> 2]);
+                        if (lane < (two ? 8 : 4)) {
+                            int bx, by;
+                            sw_blk_xy(lane < 4 ? q_i4 : i4b, bx, by);
+                            const int vx = clip3((int)s.mv4[(by >> 2) * 4 + (bx >> 2)][0], lox, hix), vy = clip3((int)s.mv4[(by >> 2) * 4 + (bx >> 2)][1], loy, hiy);
+                            const int r = by + (lane & 3), qx = vx & 3, qy = vy & 3, idx = qy * 4 + qx;
+                            const ptrdiff_t base = oy + (ptrdiff_t)((vy >> 2) + r) * a.sy + (vx >> 2) + bx + (ptrdiff_t)by_;
+                            const u8 *pa = refs.y[ri][c_qpel_a[idx]] + base + (qy == 3) * a.sy, *pb = refs.y[ri][c_qpel_b[idx]] + base + (qx == 3);
+#pragma unroll
+                            for (int i = 0; i < 4; i++) s.fd[FDY + r * FD + bx + i] = (idx & 5) ? (u8)(((int)pa[i] + (int)pb[i] + 1) >> 1) : pa[i];
+                        }
+                        WAVE_SYNC();
+                    }
+                    sw_luma4x4_fwd(s, a, Q, tq, 1, false, lane, nullptr, 0, 1 << (q_i4 >> 2), m16);
+                    const int nz0 = UNI(s.score[q_i4]) >> 8, nz1 = two ? UNI(s.score[i4b]) >> 8 : 0;
+                    if (lane == 0) { s.nnz[q_i4] = (u8)nz0; if (two) s.nnz[i4b] = (u8)nz1; }
+                    WAVE_SYNC();
+                    if (nz0 | nz1) sw_luma4x4_add(s, lane, 1 << (q_i4 >> 2), (nz0 ? 1 << q_i4 : 0) | (nz1 ? 1 << i4b : 0));
+                    int ssd, pix = 0;
+                    {
+                        int acc = 0;
+                        const int r = lane >> 2, x = (lane & 3) * 4;
+                        if (r >= q_by && r < q_by + q_h && x >= q_bx && x < q_bx + q_w) {
+#pragma unroll
+                            for (int i = 0; i < 4; i++) { const int p = (int)s.fd[FDY + r * FD + x + i], d = (int)s.fe[r * 16 + x + i] - p; acc += d * d; pix += p; }
+                        }
+                        ssd = wave_sum(acc);
+                    }
+                    if (rd.psy_rd) {                                 // size > PIXEL_8x8: |SATD of the sub-block against zero - its DC / 2 - the source's|
+                        const int dc = wave_sum(pix) >> 1;
+                        int sat = 0, f4 = 0;
+                        if (lane < (two ? 2 : 1)) {
+                            int bx, by;
+                            sw_blk_xy(lane ? i4b : q_i4, bx, by);
+                            sat = satd_4x4(s.fd + FDY + by * FD + bx, FD, sr.zero16, 0);
+                            f4 = sr.fenc_satd[(by >> 2) * 4 + (bx >> 2)];
+                        }
+                        sat = __builtin_amdgcn_readlane(sat, 0) + __builtin_amdgcn_readlane(sat, 1);
+                        f4 = __builtin_amdgcn_readlane(f4, 0) + __builtin_amdgcn_readlane(f4, 1);
+                        ssd += rf_psy(iabs(sat - dc - f4));
+                    }
+                    c64 = rf_cost64(ssd, rf_bits(1, q_i4, q_pix), Q.lambda2);
+                } else {
                 // ---- x264_rd_cost_part, rdo.c:202-242: the partition's 8x8 blocks encoded, their distortion, x264_partition_size_cabac ----
                 const int i8 = q_i4 >> 2, n8 = q_pix == 3 ? 1 : 2, st8 = q_pix == 2 ? 2 : 1;
                 cbp_luma = 0;
@@ -313,7 +429,13 @@
                     const int b8 = i8 + k * st8, x8 = 8 * (b8 & 1), y8 = 8 * (b8 >> 1);
                     {
                         const int lox = 4 * (-16 * mbx - 24), hix = 4 * (16 * (a.mb_w - mbx - 1) + 24), loy = 4 * (-16 * mby - 24), hiy = 4 * (16 * (a.mb_h - mby - 1) + 24);
-                        const int vx = clip3(UNI(s.mv4[(y8 >> 2) * 4 + (x8 >> 2)][0]), lox, hix), vy = clip3(UNI(s.mv4[(y8 >> 2) * 4 + (x8 >> 2)][1]), loy, hiy), ri = UNI((int)s.ref8[b8]);
+                        int mvb = (y8 >> 2) * 4 + (x8 >> 2);
+                        if constexpr (SUB8) {                        // x264_mb_mc_8x8: every pixel with the vector of its 4x4 block (the block may have sub-partitions)
+                            if (lane < 16) mvb = ((y8 + (lane >> 1)) >> 2) * 4 + ((x8 + (lane & 1) * 4) >> 2);
+                            else if (lane < 48) mvb = ((y8 >> 2) + (((lane - 16) >> 3) & 1)) * 4 + (x8 >> 2) + (((lane - 16) >> 1) & 1);
+                        }
+                        const int mvbx = SUB8 ? (int)s.mv4[mvb][0] : UNI(s.mv4[mvb][0]), mvby = SUB8 ? (int)s.mv4[mvb][1] : UNI(s.mv4[mvb][1]);
+                        const int vx = clip3(mvbx, lox, hix), vy = clip3(mvby, loy, hiy), ri = UNI((int)s.ref8[b8]);
                         if (lane < 16) {
                             const int r = y8 + (lane >> 1), x = x8 + (lane & 1) * 4;
                             const int qx = vx & 3, qy = vy & 3, idx = qy * 4 + qx;
@@ -462,7 +584,10 @@
                     const int s4 = (int)((u32)sum >> 1), s8 = (int)(sum >> 34);
                     ssd += rf_psy((iabs(s4 - f4) + iabs(s8 - f8)) >> 1);
                 }
-                const unsigned long long c64 = rf_cost64(ssd, rf_bits(0, i8, q_pix), Q.lambda2);
+                c64 = rf_cost64(ssd, rf_bits(0, i8, q_pix), Q.lambda2);
+                }
+                if (SUB8 && rf_kind == 4) { if (c64 < rf_best) { rf_best = c64; q_dir = q_j; } q_j++; }
+                else
                 if (c64 < rf_best) { rf_best = c64; q_bmx = q_cx; q_bmy = q_cy; if (q_tag != -3) q_dir = q_tag; }
             }
         } else

@@ -2,6 +2,9 @@
 // (k_slice_sweep, k_lossless_raster and k_psy_raster).  In scope: the kernel's parameters (SwArgs a, SwRefs refs_k, SwRd rd_k, const SwDesc *tab) and the
 // compile-time constants LL, RD, BS, TD, RF, CH, PT described there.
     static_assert(!CH || RD, "the chain table belongs to the raster variant");
+    // SUB8: the kernels that code sub-8x8 P partitions under the RD levels (X264_ANALYSE_PSUB8x8 with subme 6-9) and keep the macroblock's own
+    // non_zero_count / mvd cache entries from macroblock to macroblock and frame to frame (x264hip_slice_rd.mb_carry): the lossy refinement kernels
+    constexpr bool SUB8 = RF && !LL;
     SwRd rd_l;
     if constexpr (CH) {
         typedef const __attribute__((address_space(4))) SwDesc *desc_p;
@@ -105,6 +108,19 @@
         sr.zz8[lane] = c_scan8[0][lane]; sr.w8z[lane] = sw_w8z(lane);
         cd_load_tables(lane);
     }
+    if constexpr (SUB8) {
+        // h->mb.cache.non_zero_count / mvd[0] at the macroblock's own blocks as the chain's previous frame left them: x264_macroblock_cache_load
+        // rewrites the neighbours' entries only, and a partial trial encode that runs before any full one prices against the leftovers
+        // (R/encoder/analyse.c:1976-1977; oracle/slice_oracle.c: carry_nnz / carry_mvd)
+        if (rd.mb_carry) {
+            const u8 *cp = rd.mb_carry + (size_t)bz * 160;
+            if (lane < 32) s.nnz[lane] = cp[lane];
+            if (lane < 16) {
+                const int k = 12 + (lane & 3) + 8 * (lane >> 2);
+                sr.cmvd[k][0] = ((const i16 *)(cp + 32))[2 * lane]; sr.cmvd[k][1] = ((const i16 *)(cp + 32))[2 * lane + 1];
+            }
+        }
+    }
     WAVE_SYNC();
 
     int nr_acc4 = 0, nr_acc8 = 0, nr_n4 = 0, nr_n8 = 0;      // --nr: this row's additions to nr_residual_sum (lane = coefficient index) / nr_count
@@ -207,6 +223,10 @@
                 WAVE_SYNC();
             }
             // ---- what the entropy coder reads of the neighbours (R/common/macroblock.c:896-1010,1129-1160) ----
+            if constexpr (SUB8) {   // with the carry the macroblock's own entries (12 + x + 8 y) stay as the last macroblock left them, like s.nnz
+                const bool own = rd.mb_carry && lane >= 12 && lane < 40 && ((lane - 12) & 7) < 4;
+                if (lane < 48 && !own) { sr.cmvd[lane][0] = 0; sr.cmvd[lane][1] = 0; }
+            } else
             if (lane < 48) { sr.cmvd[lane][0] = 0; sr.cmvd[lane][1] = 0; }
             WAVE_SYNC();
             if (nb & NB_TOP) {
@@ -669,6 +689,8 @@
             // by the lane itself or with v_writelane -- no LDS round trip, no barrier.
             int cref_v = -2, cmvx_v = 0, cmvy_v = 0, pme_v = 0;
             int sub_mx = 0, sub_my = 0, sub_cost = 0, sub_px = 0, sub_py = 0, sub_t = D_L0_8x8;      // sub-8x8 records (lanes 0..31) and chosen type (lanes 0..3)
+            int sub_cst = MX_COST_MAX;          // (SUB8) lane 4 i + t: a->l0.i_cost4x4[i] / i_cost8x4[i] / i_cost4x8[i] (t = D_L0_4x4, 8x4, 4x8), COST_MAX where not searched
+            (void)sub_cst;
             if (is_p && (RD || (a.flags_inter & 0x10))) {
                 // the full motion cache for x264_mb_predict_mv on partitions: -2 = not available, neighbours as cache_load leaves them
                 if ((nb & NB_TOP) && lane >= 4 && lane < 8) {
@@ -946,6 +968,7 @@
                                     }
                                     int cst = sum + (Q.lambda * refs.ref_bits[r]) + Q.lambda * (t == 0 ? 5 : 3);          // i_sub_mb_p_cost_table
                                     if (a.chroma_me && a.subme >= 5) cst += sw_sub_chroma(s, refs, a, r, i, t, rec0, sub_mx, sub_my, satd, oc, bc_, lane);
+                                    if constexpr (SUB8) { if (lane == 4 * i + t) sub_cst = cst; }
                                     if (t == 0) {
                                         if (!(cst < pme(i, 2))) break;
                                         c8 = cst; subt = D_L0_4x4;
@@ -1085,6 +1108,8 @@
                         int rf_kind = 0, rf_i = 0, rf_n = 0, rf_old16 = 0, rf_best16 = 0, rf_thr = 0;
                         u32 rf_list = 0;
                         unsigned long long rf_best = 0;
+                        int rf_sub = 0, rf_k = 0;       // (SUB8) the sub-partitions of step 5 are chosen; the sub-block the refinement is at
+                        (void)rf_sub; (void)rf_k;
                         int q_st = 0, q_j = 0, q_it = 0, q_dir = -2, q_odir = 0, q_tag = 0, q_after_pm = 0;
                         int q_bmx = 0, q_bmy = 0, q_omx = 0, q_omy = 0, q_pmx = 0, q_pmy = 0, q_m0x = 0, q_m0y = 0, q_mvpx = 0, q_mvpy = 0, q_cx = 0, q_cy = 0;
                         int q_pix = 0, q_bx = 0, q_by = 0, q_w = 16, q_h = 16, q_slot = -1, q_ref = 0, q_i4 = 0, q_satds = 0;
@@ -1103,6 +1128,15 @@
                             const int slot8 = part == D_16x8 ? 4 + by8 : part == D_8x16 ? 6 + bx8 : by8 * 2 + bx8;
                             int vx = __shfl(pme_v, slot * 8 + 0, 64), vy = __shfl(pme_v, slot * 8 + 1, 64), vr = __shfl(pme_v, slot8 * 8 + 4, 64);
                             if (part == D_16x16) { vx = me16x; vy = me16y; vr = me16r; }
+                            if constexpr (SUB8) {
+                                // x264_mb_cache_mv_p8x8: an 8x8 block with sub-partitions takes its vectors from the records of its type (sub_t)
+                                if (part == D_8x8 && (a.flags_inter & 0x20)) {
+                                    const int i8 = (by4 >> 1) * 2 + (bx4 >> 1), st = __shfl(sub_t, i8, 64);
+                                    const int rec = st == D_L0_4x4 ? 4 * i8 + (by4 & 1) * 2 + (bx4 & 1) : st == D_L0_8x4 ? 16 + 2 * i8 + (by4 & 1) : 24 + 2 * i8 + (bx4 & 1);
+                                    const int sx = __shfl(sub_mx, rec, 64), sy = __shfl(sub_my, rec, 64);
+                                    if (st != D_L0_8x8) { vx = sx; vy = sy; }
+                                }
+                            }
                             if (lane < 16) { s.mv4[lane][0] = (i16)vx; s.mv4[lane][1] = (i16)vy; }
                             if (lane < 4) s.ref8[lane] = (signed char)vr;
                             {   // the motion cache's copy of block 12 (raster block 10, 8x8 block 3) follows the candidate
@@ -1155,6 +1189,11 @@
                             } else if (step == 5) {
                                 if (!(c8x8 <= rd_thresh)) { c8x8 = MX_COST_MAX; continue; }
                                 type = T_P_8x8; part = D_8x8;
+                                if constexpr (SUB8) {
+                                    // X264_ANALYSE_PSUB8x8 (analyse.c:1966-1996): every 8x8 block's sub-partition by x264_rd_cost_part first -- in
+                                    // slice_refine.h (rf_kind 4), where the one copy of the partial encode is; it comes back here with rf_sub set
+                                    if ((a.flags_inter & 0x20) && !rf_sub) { rf_kind = 4; rf_i = 0; q_st = 0; step = 10; continue; }
+                                }
                             } else if (step == 6) {
                                 final_type = T_P_L0; final_part = 16; i_cost = rd16;
                                 if (c16x8 < i_cost) { i_cost = c16x8; final_part = 14; }
@@ -1162,6 +1201,9 @@
                                 if (c8x8 < i_cost) { i_cost = c8x8; final_part = 13; final_type = T_P_8x8; }
                                 type = final_type; part = final_part;
                                 if (!(i_cost < MX_COST_MAX) || !a.transform8x8) continue;        // x264_mb_analyse_transform_rd, :2127-2150
+                                if constexpr (SUB8) {                    // x264_mb_transform_8x8_allowed: not with a sub-partition below 8x8
+                                    if (type == T_P_8x8) { sub_t_mb = sub_t; if (__ballot(lane < 4 && sub_t != D_L0_8x8) != 0) continue; }
+                                }
                                 t8 = !t8;
                             } else if (step == 7) {                                                // x264_intra_rd, :845-874 (threshold COST_MAX in an I slice)
                                 if (!(satd_i16 <= (is_p ? satd_inter * 5 / 4 : MX_COST_MAX))) { satd_i16 = MX_COST_MAX; continue; }
@@ -1332,6 +1374,11 @@
                 mb_qp = last_qp;
             }
             // x264_macroblock_cache_save's QP rules (R/common/macroblock.c:1244-1272): a macroblock without coefficients has no QP of its own
+            if (SUB8 && type == T_I_PCM) {
+                // the cache keeps the last trial's counts for the next macroblock (x264_macroblock_encode clears the luma DC's and returns); the 16s
+                // x264_macroblock_cache_save reports go to the frame's arrays alone, below
+                mb_qp = 0; last_dqp = 0; if (lane == 24) s.nnz[24] = 0; WAVE_SYNC();
+            } else
             if (type == T_I_PCM) { mb_qp = 0; last_dqp = 0; if (lane < 27) s.nnz[lane] = 16; WAVE_SYNC(); }
             else {
                 if (type != T_I_16x16 && cbp_luma == 0 && cbp_chroma == 0) mb_qp = last_qp;
@@ -1365,7 +1412,7 @@
             a.ref[(size_t)mb * 4 + lane] = rv;
             if (lane & 1) s.left_r8[lane >> 1] = rv;
         }
-        if (lane < 27) (a.nnz + 27 * cb)[(size_t)mb * 27 + lane] = IS_SKIP_T(type) ? (u8)0 : s.nnz[lane];
+        if (lane < 27) (a.nnz + 27 * cb)[(size_t)mb * 27 + lane] = IS_SKIP_T(type) ? (u8)0 : SUB8 && type == T_I_PCM ? (u8)16 : s.nnz[lane];
         if (lane < 4) (a.sub_partition + 4 * cb)[(size_t)mb * 4 + lane] = (signed char)(type == T_P_8x8 ? sub_t_mb : BS && type == T_B_8x8 ? (int)sb.sub[lane] : 0);
         if constexpr (BS) {     // list 1 of x264_macroblock_cache_save, h->mb.skipbp, and what the next macroblock sees to its left
             if (lane < 16) {
@@ -1428,7 +1475,7 @@
             } else if (lane < 24) {
                 const int j = lane - 16;
                 const int idx = j < 4 ? (j == 0 ? 5 : j == 1 ? 7 : j == 2 ? 13 : 15) : 16 + 4 * ((j - 4) >> 1) + 1 + 2 * (j & 1);
-                sr.left_nz[j] = IS_SKIP_T(type) ? (u8)0 : s.nnz[idx];
+                sr.left_nz[j] = IS_SKIP_T(type) ? (u8)0 : SUB8 && type == T_I_PCM ? (u8)16 : s.nnz[idx];
             }
             left_cbp = cbp_store; left_cpm = intra && type != T_I_PCM ? sw_fix8c(predc) : 0; left_t8 = t8;
             prev_coded = type == T_I_16x16 || (cbp_store & 0x3f);
@@ -1455,6 +1502,16 @@
   }   // rows
     if constexpr (RD) {     // x264_slice_write's end (R/encoder/encoder.c:1269-1273)
         if (rd.write && lane == 0) { cd_encode_flush(cab, rd.i_frame + bz * rd.i_frame_stride); rd.payload_len[bz] = (int)(cab.p - payload0); }
+        if constexpr (SUB8) {       // the cache's own entries as the frame's last macroblock leaves them: the chain's next frame starts from them
+            if (rd.mb_carry) {
+                u8 *cp = rd.mb_carry + (size_t)bz * 160;
+                if (lane < 32) cp[lane] = lane < 27 ? s.nnz[lane] : (u8)0;
+                if (lane < 16) {
+                    const int k = 12 + (lane & 3) + 8 * (lane >> 2);
+                    ((i16 *)(cp + 32))[2 * lane] = sr.cmvd[k][0]; ((i16 *)(cp + 32))[2 * lane + 1] = sr.cmvd[k][1];
+                }
+            }
+        }
         if constexpr (TD) if (rd.direct_score && lane == 0) { rd.direct_score[2 * bz] = dscore0; rd.direct_score[2 * bz + 1] = dscore1; }
         if constexpr (TD) {
             if (rd.stale && lane == 30) { i16 *sp = rd.stale + (size_t)bz * 8; for (int k = 0; k < 6; k++) sp[k] = sb.stale[k]; }

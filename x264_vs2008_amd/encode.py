@@ -230,6 +230,9 @@ def check_built(p):
     if not p.cabac and p.subpel_refine >= 6:
         raise ValueError("--no-cabac with --subme %d: the RD levels price CAVLC bits with a counting twin of the writer, which is not built "
                          "(--subme 5 and below are)" % p.subpel_refine)
+    if p.inter & 0x20 and p.subpel_refine >= 6 and p.bframe:
+        raise ValueError("--partitions with p4x4 at --subme %d together with --bframes %d: sub-8x8 partitions under the RD levels are built for I / P "
+                         "streams (--bframes 0); the B kernels do not keep the cache entries a macroblock leaves behind" % (p.subpel_refine, p.bframe))
 
 
 def encode_streams(lib, p, sources, n_frames, sinks, psnr=0, ssim=0, verbose=False, stats=None, observe=None, cabac_pass=None):
@@ -279,7 +282,9 @@ def encode_streams(lib, p, sources, n_frames, sinks, psnr=0, ssim=0, verbose=Fal
         # x264_slicetype_decide has nothing to decide: an IDR every keyint frames, P frames between, constant QP
         if cabac_pass is None:
             cabac_pass = bool(p.cabac and p.subpel_refine < 6 and not p.trellis and not p.aq_mode and p.qp_constant != 0)
-        enc = sl.ChainEncoder(lib, w, h, cq, batch=B, write=1, cabac_pass=cabac_pass or None, **common, **measure)
+        # --partitions all at --subme 6..9: the chain's record of cache leftovers (x264hip_slice_rd.mb_carry); the frame queue's encoder turns it on itself
+        carry = bool(p.inter & 0x20 and p.subpel_refine >= 6 and p.qp_constant != 0)
+        enc = sl.ChainEncoder(lib, w, h, cq, batch=B, write=1, cabac_pass=cabac_pass or None, mb_carry=carry, **common, **measure)
         try:
             for t in range(n_frames):
                 for b, s in enumerate(sources):

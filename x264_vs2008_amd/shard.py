@@ -48,6 +48,9 @@ def encode_clip(hip, cqm, frames, keyint, rank=0, world=1, **options):
     from . import slice as sl
     if options.get("lanes"):
         raise ValueError("encode_clip: lanes are a scheduling option of single-stream chains, not of a sharded clip")
+    if options.get("mb_carry") or (options.get("inter", 0) & 0x20 and options.get("subme", 0) >= 6):
+        raise ValueError("encode_clip: sub-8x8 partitions (inter & 0x20) with the RD levels (subme >= 6): the macroblock cache's leftovers "
+                         "(x264hip_slice_rd.mb_carry) pass from every frame of the stream to the next, across the GOPs a sharded clip codes side by side")
     n = len(frames)
     gops = gop_bounds(n, keyint)
     mine = [i for i in range(len(gops)) if i % world == rank]

@@ -103,7 +103,7 @@ class ChainEncoder:
                  transform8x8=0, fast_pskip=1, dct_decimate=1, chroma_me=1, cabac=0, deblock=0, alpha_c0=0, beta=0,
                  chroma_qp_offset=0, keyint=0, mixed_refs=0, noise_reduction=0, mv_range=0,
                  trellis=0, psy_rd=0.0, aq_mode=0, aq_strength=1.0, write=0, cabac_init_idc=0, qp_min=0, qp_max=51, payload_cap=0, raster=None,
-                 bframes=0, weightb=0, direct_pred=1, lanes=0, levels=True, psnr=0, ssim=0, mb_stats=0, psy_trellis=0.0, cabac_pass=None):
+                 bframes=0, weightb=0, direct_pred=1, lanes=0, levels=True, psnr=0, ssim=0, mb_stats=0, psy_trellis=0.0, cabac_pass=None, mb_carry=False):
         self.lib = lib
         self.lossless = int(qp == 0)
         # param.analyse.b_psnr / b_ssim: the quality pass (quality.py) behind every frame -- a B frame's behind its sweep, on its unfiltered
@@ -175,6 +175,14 @@ class ChainEncoder:
             # x264hip_slice_rd.psy_carry: h->mb.pic.fenc_dct4 | fenc_dct8, which the reference never clears either; zero like its x264_t
             if self.psy_trellis_fix:
                 rb["psy_carry"] = DeviceArray(lib, (B, 512), np.int16)
+            # x264hip_slice_rd.mb_carry: the macroblock's own non_zero_count / mvd cache entries, which the reference never resets either; with
+            # sub-8x8 partitions under the RD levels the first partial trial encode of a macroblock prices against them.  Zero like its x264_t,
+            # one record per chain, handed to every sweep and never reset.  Off by default: that combination then stays refused by the sweep
+            if mb_carry:
+                if bframes and inter & 0x20 and subme >= 6:
+                    raise ValueError("mb_carry (sub-8x8 partitions with the RD levels) does not go with bframes: the B kernels do not keep the cache "
+                                     "entries a macroblock leaves behind, and the sweep refuses a B slice of such a chain")
+                rb["mb_carry"] = DeviceArray(lib, (B, 160), np.uint8, np.zeros((B, 160), np.uint8))
             self.rd_bufs = rb
             self.payload_cap = cap
         if self.cavlc and not levels:
@@ -292,7 +300,8 @@ class ChainEncoder:
                        cost_mv_all=rb["cost_mv_all"].ptr, unquant4_mf=rb["unquant4_mf"].ptr, unquant8_mf=rb["unquant8_mf"].ptr,
                        payload=rb["payload"].ptr, payload_cap=self.payload_cap, payload_len=rb["payload_len"].ptr, mb_bits=rb["mb_bits"].ptr,
                        stale=rb["stale"].ptr, i_frame_stride=i_frame_stride, psy_trellis=self.psy_trellis_fix,
-                       psy_carry=rb["psy_carry"].ptr if "psy_carry" in rb else None)
+                       psy_carry=rb["psy_carry"].ptr if "psy_carry" in rb else None,
+                       mb_carry=rb["mb_carry"].ptr if "mb_carry" in rb else None)
 
     def filter_kept(self, c, recon, s):
         """x264_fdec_filter_row for a whole kept frame, enqueued on context c: loop filter (from the x264hip_mb_state s), borders, half-pel

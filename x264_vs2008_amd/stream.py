@@ -50,6 +50,13 @@ class StreamEncoder(ChainEncoder):
         if kw.get("lanes"):
             raise ValueError("StreamEncoder: the chains of a step already run side by side; lanes belong to the lock-step encoder")
         self._direct_auto_ok = True                     # --direct auto: the running scores live here (c_dscore)
+        # sub-8x8 partitions with the RD levels (--partitions all --subme 6..9): every chain's frames are swept in its coding order here, the
+        # given-up attempts of the post-encode scene cut included, so the chain's record of cache leftovers (x264hip_slice_rd.mb_carry) is on
+        if kw.get("inter", 0) & 0x20 and kw.get("subme", 0) >= 6 and kw.get("qp", 26) != 0:
+            if kw.get("bframes", 0):
+                raise ValueError("StreamEncoder: sub-8x8 partitions (inter & 0x20) with the RD levels (subme >= 6) and bframes > 0: the B kernels do not "
+                                 "keep the cache entries a macroblock leaves behind (x264hip_slice_rd.mb_carry); I / P streams are built")
+            kw["mb_carry"] = True
         super().__init__(lib, width, height, cqm, batch=batch, **kw)
         if not self.raster or not (self.rd_opt["write"] or self.cavlc):
             raise ValueError("StreamEncoder: the chain-table sweep is the raster variant with the entropy coder in the loop, or followed by the CAVLC pass")
@@ -500,6 +507,10 @@ class AsyncStreamEncoder(StreamEncoder):
             raise ValueError("AsyncStreamEncoder: --nr: a launch's B kernel ends on a stream of its own, and a chain's noise-reduction sums must be "
                              "complete before its update (x264hip_noise_reduction_update_chains) and the update before the chain's next sweep: that "
                              "ordering is not built here; StreamEncoder and ChainEncoder code --nr")
+        if kw.get("inter", 0) & 0x20 and kw.get("subme", 0) >= 6:
+            raise ValueError("AsyncStreamEncoder: sub-8x8 partitions (inter & 0x20) with the RD levels (subme >= 6): the chain's record of cache leftovers "
+                             "(x264hip_slice_rd.mb_carry) must pass from each sweep of a chain to the next in coding order, and launches of different "
+                             "ages overlap here; StreamEncoder and ChainEncoder code it")
         bf = kw.get("bframes", 0)
         b_adapt = kw.get("b_adapt", 1)
         delay = (max(bf, 3) * 4 if b_adapt == 2 and bf else bf)
