@@ -119,6 +119,24 @@ typedef struct {
 int x264hip_cavlc_write_chains(x264hip_frame_ctx *c, const x264hip_chain_cavlc *entries, int n, void *staging_host, void *table_dev);
 size_t x264hip_chain_cavlc_bytes(void);
 
+/* The same two calls with every lane writing: the macroblock-parallel CAVLC pass.  x264hip_cavlc_write_frame and _chains put one lane of one
+ * wavefront on a slice; CAVLC has no adaptive state, so a macroblock's bits depend on the state arrays alone and only their position in the
+ * slice is serial -- a prefix sum.  Three phases on the context's stream: count (one lane per macroblock: bit lengths, after a short kernel
+ * that leaves every block's coefficient total for nC), scan (per slice: offsets, skip runs, mb_bits, payload_len, the aborts, and the zeroing
+ * of the bytes about to be written), place (one lane per macroblock: its bits at its offset, words shared with a neighbour merged with
+ * atomic OR).  Same parameter records, same bytes, payload_len, mb_bits, refusals and messages as the serial calls, the same aborts (I_PCM, a
+ * slot too small by the same rule; payload_len 0 and nothing placed), and no limit on the macroblocks per row.  Nothing the caller has zeroed
+ * is relied on; no byte outside the chain's slot is touched and the slot's X264HIP_PAYLOAD_LEAD bytes keep their values.  (Place merges a
+ * macroblock's first and last 32-bit word with a 4-byte-aligned atomic OR.  The last word ends inside the slot: at least 20 bytes stay free
+ * behind a slice that passed the space check.  Where a slot's start is no multiple of 4 -- a payload_cap that is none -- the first word of
+ * the slice takes in up to 3 of the slot's own lead bytes: zeros are ORed into them, so they are read and written back unchanged, and must
+ * not be written by anyone else while the pass runs.)  scratch_dev:
+ * x264hip_cavlc_mp_scratch_bytes(c, n_slices) device bytes -- n_slices: the context's batch for _frame_mp, the table's entries for
+ * _chains_mp --, left alone until the stream has passed the call.  At most 65535 slices per call.  Opt-in: nothing selects this pass by itself. */
+int x264hip_cavlc_write_frame_mp(x264hip_frame_ctx *c, const x264hip_mb_state *st, const x264hip_cavlc_params *p, void *scratch_dev);
+int x264hip_cavlc_write_chains_mp(x264hip_frame_ctx *c, const x264hip_chain_cavlc *entries, int n, void *staging_host, void *table_dev, void *scratch_dev);
+size_t x264hip_cavlc_mp_scratch_bytes(const x264hip_frame_ctx *c, int n_slices);
+
 #ifdef __cplusplus
 }
 #endif

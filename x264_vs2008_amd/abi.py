@@ -330,6 +330,9 @@ PROTOTYPES = {
     "x264hip_cabac_write_frame": "i:ppp",
     "x264hip_cavlc_write_chains": "i:ppipp",
     "x264hip_chain_cavlc_bytes": "z:",
+    "x264hip_cavlc_write_frame_mp": "i:pppp",
+    "x264hip_cavlc_write_chains_mp": "i:ppippp",
+    "x264hip_cavlc_mp_scratch_bytes": "z:pi",
     # include/x264hip_stream.h
     "x264hip_encoder_params_default": "v:p",
     "x264hip_validate_parameters": "i:p",

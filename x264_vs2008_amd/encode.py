@@ -59,6 +59,7 @@ def build_parser():
     a("--scenecut", type=int, default=40)
     a("--pre-scenecut", action="store_true")
     a("--no-cabac", action="store_true")
+    a("--cavlc-mp", action="store_true", help="with --no-cabac: write the slices with the macroblock-parallel CAVLC pass (same bytes)")
     a("--no-deblock", "--nf", action="store_true")
     a("-f", "--deblock", default=None, help="alpha:beta (negative alpha: write --deblock=-1:2)")
     a("-A", "--partitions", "--analyse", default=None, help="p8x8,p4x4,b8x8,i8x8,i4x4 / none / all")
@@ -235,7 +236,7 @@ def check_built(p):
                          "streams (--bframes 0); the B kernels do not keep the cache entries a macroblock leaves behind" % (p.subpel_refine, p.bframe))
 
 
-def encode_streams(lib, p, sources, n_frames, sinks, psnr=0, ssim=0, verbose=False, stats=None, observe=None, cabac_pass=None):
+def encode_streams(lib, p, sources, n_frames, sinks, psnr=0, ssim=0, verbose=False, stats=None, observe=None, cabac_pass=None, cavlc_mp=None):
     """p: validated parameters (mux.encoder_params); sources: readers of equal picture size; sinks: binary files, one per source.
     psnr / ssim: measure every coded frame (x264hip_frame_report_*); stats: a list that receives one quality.Stat per stream (the caller prints
     its summary and closes it); verbose: x264_encoder_frame_end's line per frame on stderr; observe(enc, chain, frame, slice type, picture, state,
@@ -243,7 +244,9 @@ def encode_streams(lib, p, sources, n_frames, sinks, psnr=0, ssim=0, verbose=Fal
     cabac_pass: who writes a CABAC slice of a stream without lookahead (constant QP, no B frames, no scene cuts) -- None: the pass behind the
     sweep (ChainEncoder(cabac_pass=True)) below the RD levels, without trellis and adaptive quantisation, not lossless -- where the sweep in
     front of it is the macroblock-parallel one, measured faster; under --aq-mode 1 both choices code a frame on one wavefront
-    per chain and nothing has been measured, so the in-loop writer stays; True / False force it either way.  The bytes are the same."""
+    per chain and nothing has been measured, so the in-loop writer stays; True / False force it either way.  The bytes are the same.
+    cavlc_mp: who writes a --no-cabac slice wherever the CAVLC pass runs -- True: the macroblock-parallel pass (ChainEncoder(cavlc_mp=True):
+    count, scan, place), None / False: the serial pass; a ValueError where no CAVLC pass runs (CABAC).  The bytes are the same."""
     check_built(p)
     from .quality import Stat
     if stats is not None:
@@ -284,7 +287,7 @@ def encode_streams(lib, p, sources, n_frames, sinks, psnr=0, ssim=0, verbose=Fal
             cabac_pass = bool(p.cabac and p.subpel_refine < 6 and not p.trellis and not p.aq_mode and p.qp_constant != 0)
         # --partitions all at --subme 6..9: the chain's record of cache leftovers (x264hip_slice_rd.mb_carry); the frame queue's encoder turns it on itself
         carry = bool(p.inter & 0x20 and p.subpel_refine >= 6 and p.qp_constant != 0)
-        enc = sl.ChainEncoder(lib, w, h, cq, batch=B, write=1, cabac_pass=cabac_pass or None, mb_carry=carry, **common, **measure)
+        enc = sl.ChainEncoder(lib, w, h, cq, batch=B, write=1, cabac_pass=cabac_pass or None, mb_carry=carry, cavlc_mp=cavlc_mp, **common, **measure)
         try:
             for t in range(n_frames):
                 for b, s in enumerate(sources):
@@ -309,7 +312,7 @@ def encode_streams(lib, p, sources, n_frames, sinks, psnr=0, ssim=0, verbose=Fal
     enc = StreamEncoder(lib, w, h, cq, batch=B, n_frames=n_frames, crf=p.rf_constant if p.rc_method == mux.RC_CRF else None, b_adapt=p.bframe_adaptive,
                         bframe_bias=p.bframe_bias, keyint_min=p.keyint_min, scenecut_threshold=p.scenecut_threshold, pre_scenecut=p.pre_scenecut,
                         ip_factor=p.ip_factor, pb_factor=p.pb_factor, qcompress=p.qcompress, qp_step=p.qp_step, bframes=p.bframe, weightb=p.weighted_bipred,
-                        direct_pred=p.direct_mv_pred, **common, **measure)
+                        direct_pred=p.direct_mv_pred, cavlc_mp=cavlc_mp, **common, **measure)
 
     def fill(pic, f):
         for b, s in enumerate(sources):
@@ -372,7 +375,7 @@ def main(argv=None):
     stats = None if rf["quiet"] else []
     t0 = time.time()
     try:
-        done = encode_streams(lib, p, sources, n, sinks, psnr=rf["psnr"], ssim=rf["ssim"], verbose=rf["verbose"], stats=stats)
+        done = encode_streams(lib, p, sources, n, sinks, psnr=rf["psnr"], ssim=rf["ssim"], verbose=rf["verbose"], stats=stats, cavlc_mp=o.cavlc_mp or None)
     except (ValueError, RuntimeError) as ex:
         raise SystemExit("encode: " + str(ex))
     finally:

@@ -103,7 +103,8 @@ class ChainEncoder:
                  transform8x8=0, fast_pskip=1, dct_decimate=1, chroma_me=1, cabac=0, deblock=0, alpha_c0=0, beta=0,
                  chroma_qp_offset=0, keyint=0, mixed_refs=0, noise_reduction=0, mv_range=0,
                  trellis=0, psy_rd=0.0, aq_mode=0, aq_strength=1.0, write=0, cabac_init_idc=0, qp_min=0, qp_max=51, payload_cap=0, raster=None,
-                 bframes=0, weightb=0, direct_pred=1, lanes=0, levels=True, psnr=0, ssim=0, mb_stats=0, psy_trellis=0.0, cabac_pass=None, mb_carry=False):
+                 bframes=0, weightb=0, direct_pred=1, lanes=0, levels=True, psnr=0, ssim=0, mb_stats=0, psy_trellis=0.0, cabac_pass=None, mb_carry=False,
+                 cavlc_mp=None):
         self.lib = lib
         self.lossless = int(qp == 0)
         # param.analyse.b_psnr / b_ssim: the quality pass (quality.py) behind every frame -- a B frame's behind its sweep, on its unfiltered
@@ -136,6 +137,13 @@ class ChainEncoder:
                    "levels=False (the pass reads the coefficient levels)" if not levels else "lanes" if lanes else None)
             if why:
                 raise ValueError("cabac_pass=True does not go with %s" % why)
+        # cavlc_mp: who writes a CAVLC slice wherever the CAVLC pass runs -- True: the macroblock-parallel pass (x264hip_cavlc_write_frame_mp /
+        # _chains_mp: count, scan, place; every lane writes), None / False: the serial one (one lane per slice).  The bytes are the same
+        self.cavlc_mp = bool(cavlc_mp)
+        self._cavlc_mp_scratch = {}                    # per context (the main one, a lane's): the pass's scratch, live while its stream runs
+        if self.cavlc_mp and not self.cavlc:
+            raise ValueError("cavlc_mp=True does not go with %s: it selects the writer of the CAVLC pass (cabac=0, write=1, below the RD levels)" % (
+                "cabac=1" if cabac else "write=0" if not write else "subme >= 6 or trellis (CAVLC under the RD levels is not built)"))
         in_loop = bool(write and not self.cavlc and not self.cabac_pass)
         self.raster = bool(subme >= 6 or trellis or aq_mode or in_loop or (self.cavlc and bframes)) if raster is None else bool(raster)
         self.rd_opt = dict(trellis=trellis, aq_mode=aq_mode, aq_strength=aq_strength, write=int(bool(in_loop or subme >= 6 or trellis)),
@@ -384,7 +392,10 @@ class ChainEncoder:
             cp = CavlcParams(slice_type=stype, n_ref0=len(refs), analyse_inter=o["inter"], transform8x8=o["transform8x8"], cqm_custom=0,
                              payload=rb["payload"].ptr, payload_cap=self.payload_cap, payload_len=rb["payload_len"].ptr, mb_bits=rb["mb_bits"].ptr,
                              slice_qp=qp)
-            c.check(L.x264hip_cavlc_write_frame(c.h, C.byref(state.st), C.byref(cp)), "cavlc_write_frame")
+            if self.cavlc_mp:
+                c.check(L.x264hip_cavlc_write_frame_mp(c.h, C.byref(state.st), C.byref(cp), self.cavlc_mp_scratch(c).p), "cavlc_write_frame_mp")
+            else:
+                c.check(L.x264hip_cavlc_write_frame(c.h, C.byref(state.st), C.byref(cp)), "cavlc_write_frame")
             self.last_bufs = rb
         if self.cabac_pass:                            # x264_macroblock_write_cabac for every macroblock of every chain, from the state just written
             rb = self.last_bufs if self.raster else self.rd_bufs
@@ -406,6 +417,13 @@ class ChainEncoder:
         if is_b and self.quality is not None:              # a disposable B frame is never filtered: measured as the sweep left it, on the stream it ran on
             self.measure(c, fenc, recon, state, stype)
         return stype, qp, state
+
+    def cavlc_mp_scratch(self, c):
+        """The device scratch of the macroblock-parallel CAVLC pass on context c, allocated on first use: x264hip_cavlc_mp_scratch_bytes for
+        c.batch slices, the most one call writes (every chain's slice of a frame, or a chain table with at most one entry per chain)."""
+        if id(c) not in self._cavlc_mp_scratch:
+            self._cavlc_mp_scratch[id(c)] = DeviceArray(self.lib, (self.lib.x264hip_cavlc_mp_scratch_bytes(c.h, c.batch),), np.uint8)
+        return self._cavlc_mp_scratch[id(c)]
 
     def measure(self, c, fenc, recon, state, stype):
         """The quality pass for the frame just coded, enqueued on context c (the main one or a lane's); reports() reads it after the sync."""
@@ -484,8 +502,9 @@ class ChainEncoder:
         self.lanes = []
         for s in self.states:
             s.free()
-        for d in self.cost.values():
+        for d in list(self.cost.values()) + list(self._cavlc_mp_scratch.values()):
             d.free()
+        self._cavlc_mp_scratch = {}
         for d in (self.rd_bufs or {}).values():
             d.free()
         self.cqm.free()

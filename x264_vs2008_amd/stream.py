@@ -326,7 +326,11 @@ class StreamEncoder(ChainEncoder):
             cv = (ChainCavlc * len(self._cv))()
             for k, (ci, mine, cp) in enumerate(self._cv):
                 cv[k] = ChainCavlc(ci, C.addressof(mine), C.addressof(cp))
-            c.check(L.x264hip_cavlc_write_chains(c.h, cv, len(self._cv), self.cv_host, self.cv_dev.p), "cavlc_write_chains")
+            if self.cavlc_mp:                              # (scratch for a full table: a step holds at most one entry per chain)
+                c.check(L.x264hip_cavlc_write_chains_mp(c.h, cv, len(self._cv), self.cv_host, self.cv_dev.p, self.cavlc_mp_scratch(c).p),
+                        "cavlc_write_chains_mp")
+            else:
+                c.check(L.x264hip_cavlc_write_chains(c.h, cv, len(self._cv), self.cv_host, self.cv_dev.p), "cavlc_write_chains")
         for pic_i, chains in filt.items():
             c.check(L.x264hip_frame_ctx_elements(c.h, publish(pic_i, chains), len(chains)), "frame_ctx_elements")
             self.filter_kept(c, self.pool[pic_i], self.states[pic_i].st)
