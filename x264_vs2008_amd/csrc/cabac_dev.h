@@ -4,7 +4,9 @@
 //   x264_macroblock_write_cabac (I and P)        R/encoder/cabac.c:32-1022
 // The entropy coder is a serial machine: one lane runs it while the other 63 wait, on state that lives in LDS (the 460
 // context states, the macroblock's syntax record `MbSyn`) and in registers (low / range / queue).  The kernel gathers what
-// the writer reads into an MbSyn with all lanes, then lane 0 walks it.  `rd` selects bit counting, where the reference's
+// the writer reads into an MbSyn with all lanes, then lane 0 walks it.  For the RD trials' bit count of a whole macroblock the
+// wave first ballots the nonzero masks of the coefficient arrays, and lane 0 walks the residual blocks from those instead of
+// scanning them: cabac_price.h.  `rd` selects bit counting, where the reference's
 // RDO_SKIP_BS build of the same source differs in: contexts that are not updated (_noup), bypass bins counted as 256, the
 // order in which a residual block's flags and levels are visited (cabac.c:679-763; it matters for 8x8 blocks, whose
 // significance contexts are shared between positions) and mb_qp_delta's side effect on the QP being switched off.
@@ -454,14 +456,15 @@ template <class ST, class MS, class LV> CD_FN void cw_residual(DCabac &cb, ST st
 // x264_macroblock_write_cabac, :781-1022 (I and P slices): writes (rd = 0) or counts (rd = 1: x264_macroblock_size_cabac).
 // fe: the source macroblock (Y 16x16, U 8x8, V 8x8 contiguous) for I_PCM, which is only ever written.  The caller copies the
 // source into the reconstruction for I_PCM (cabac.c:815-818).
-template <class ST, class MS, class FE> CD_FN void cw_macroblock(DCabac &cb, ST st, int rd, MS &m, FE fe, int i_frame)
+// cw_mb_head is everything in front of the residual, :781-968, shared with the trials' bit count (cabac_price.h); false: no residual follows.
+template <class ST, class MS, class FE> CD_FN bool cw_mb_head(DCabac &cb, ST st, int rd, MS &m, FE fe, int i_frame)
 {
     const int type = m.type;
     cw_mb_type(cb, st, rd, m, i_frame);
     if (!rd && type == T_I_PCM) {
         for (int i = 0; i < 384; i++) *cb.p++ = fe[i];
         cb.low = 0; cb.range = 0x1FE; cb.queue = -1; cb.outstanding = 0;
-        return;
+        return false;
     }
     if (type <= T_I_PCM) {
         if (m.pps_t8 && type != T_I_16x16) cdd_noup(cb, st, rd, 399 + m.nb_t8, m.t8);
@@ -504,8 +507,14 @@ template <class ST, class MS, class FE> CD_FN void cw_macroblock(DCabac &cb, ST 
     }
     if (type != T_I_16x16) cw_cbp(cb, st, rd, m);
     if (m.t8_allowed && m.cbp_luma) cdd_noup(cb, st, rd, 399 + m.nb_t8, m.t8);
-    if (m.cbp_luma > 0 || m.cbp_chroma > 0 || type == T_I_16x16) {
-        cw_qp_delta(cb, st, rd, m);
+    if (!(m.cbp_luma > 0 || m.cbp_chroma > 0 || type == T_I_16x16)) return false;
+    cw_qp_delta(cb, st, rd, m);
+    return true;
+}
+template <class ST, class MS, class FE> CD_FN void cw_macroblock(DCabac &cb, ST st, int rd, MS &m, FE fe, int i_frame)
+{
+    const int type = m.type;
+    if (cw_mb_head(cb, st, rd, m, fe, i_frame)) {
         if (type == T_I_16x16) {
             cw_residual(cb, st, rd, m, 0, 24, &m.lv_dc[0], 16);
             if (m.cbp_luma) for (int i = 0; i < 16; i++) cw_residual(cb, st, rd, m, 1, i, &m.lv4[i][1], 15);

@@ -628,18 +628,7 @@
         int cst = ssd_mb();
         if (type == T_B_SKIP) cst += (Q.lambda2 + 128) >> 8;
         else {
-            syn_prepare();
-            for (int k = lane; k < 460; k += 64) sr.cabac_tmp[k] = sr.cabac[k];
-            const MbSynDev y0 = make_syn();
-            WAVE_SYNC();
-            if (lane == 0) {
-                DCabac tcb = {0, 0x1FE, -1, 0, nullptr, 0};
-                MbSynDev y = y0;
-                cw_macroblock(tcb, sr.cabac_tmp, 1, y, s.fe, 0);
-                sr.tmp_i[0] = tcb.f8;
-            }
-            WAVE_SYNC();
-            const int f8 = UNI(sr.tmp_i[0]);
+            const int f8 = price_mb();
             cst += (int)(((unsigned long long)(u32)f8 * (u32)Q.lambda2 + 32768) >> 16);
         }
         t8 = t8_bak;

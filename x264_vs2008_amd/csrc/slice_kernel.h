@@ -38,6 +38,7 @@
 #include "frame_internal.h"
 #include "mb_vocab.h"
 #include "trellis_wave.h"
+#include "cabac_price.h"
 
 using namespace x264hip;
 

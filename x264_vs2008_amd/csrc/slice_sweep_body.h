@@ -658,7 +658,24 @@
             y.lv4 = (i16 (*)[16])s.lv_y; y.lv8 = (i16 (*)[64])s.lv_y8; y.lv_dc = s.lv_dc; y.lv_cdc = (i16 (*)[4])s.lv_cdc; y.lv_cac = (i16 (*)[16])s.lv_cac;
             return y;
         };
-        (void)cache_fenc_satd; (void)ssd_mb;
+        // x264_macroblock_size_cabac of an RD trial (rdo.c:139-171), priced against a copy of the live contexts: the coefficient arrays summarised
+        // by ballots of the whole wave first, then lane 0 walks the syntax (cabac_price.h)
+        auto price_mb = [&]() -> int {
+            syn_prepare();
+            for (int k = lane; k < 460; k += 64) sr.cabac_tmp[k] = sr.cabac[k];
+            const MbSynDev y0 = make_syn();
+            const CpMasks km = cp_masks([&](int q) -> cp_u64 { return __ballot(cp_mask_lane(y0, q, lane)); });
+            WAVE_SYNC();
+            if (lane == 0) {
+                DCabac tcb = {0, 0x1FE, -1, 0, nullptr, 0};
+                MbSynDev y = y0;
+                cp_macroblock(tcb, sr.cabac_tmp, y, km);
+                sr.tmp_i[0] = tcb.f8;
+            }
+            WAVE_SYNC();
+            return UNI(sr.tmp_i[0]);
+        };
+        (void)cache_fenc_satd; (void)ssd_mb; (void)price_mb;
         // a->i_satd_pcm, analyse.c:246
         const int satd_pcm = RD && !rd.psy_rd && mbrd ? (int)(((unsigned long long)(386 * 8) * (u32)Q.lambda2 + 128) >> 8) : MX_COST_MAX;
 
@@ -1276,18 +1293,7 @@
                             int c = ssd_mb();
                             if (type == T_P_SKIP) c += (Q.lambda2 + 128) >> 8;
                             else {
-                                syn_prepare();
-                                for (int k = lane; k < 460; k += 64) sr.cabac_tmp[k] = sr.cabac[k];
-                                const MbSynDev y0 = make_syn();
-                                WAVE_SYNC();
-                                if (lane == 0) {
-                                    DCabac tcb = {0, 0x1FE, -1, 0, nullptr, 0};
-                                    MbSynDev y = y0;
-                                    cw_macroblock(tcb, sr.cabac_tmp, 1, y, s.fe, 0);
-                                    sr.tmp_i[0] = tcb.f8;
-                                }
-                                WAVE_SYNC();
-                                const int f8 = UNI(sr.tmp_i[0]);
+                                const int f8 = price_mb();
                                 c += (int)(((unsigned long long)(u32)f8 * (u32)Q.lambda2 + 32768) >> 16);
                             }
                             t8 = t8_bak;
