@@ -99,7 +99,9 @@ int x264_deblock_init_hip(x264hip_deblock_function_t *pf);          /* R/common/
 typedef struct x264hip_frame_ctx x264hip_frame_ctx;
 
 typedef struct {
-    int width, height;        /* visible luma size; coded size is rounded up to 16 */
+    int width, height;        /* visible luma size, 2..16384; coded size is rounded up to 16.  A picture below 16x16 is its one coded
+                               * macroblock with the visible samples replicated: intake (upload, import), download and the encoders are
+                               * tested there (the sweep sees the 16x16 coded area); the other frame-level passes from 16x16 up */
     int mb_w, mb_h;           /* filled by x264hip_frame_ctx_new */
     int stride_y, stride_c;   /* filled by x264hip_frame_ctx_new */
     int lines_y, lines_c;     /* coded lines */
@@ -139,6 +141,31 @@ int x264hip_picture_upload(x264hip_frame_ctx *c, x264hip_picture *pic,
  * point; hip_stream NULL = the context's stream */
 int x264hip_picture_upload_async(x264hip_frame_ctx *c, x264hip_picture *pic, const uint8_t *y, int sy, const uint8_t *u, int su,
                                  const uint8_t *v, int sv, void *hip_stream);
+/* The same for pictures that already lie in DEVICE memory -- a decoder's pitched NV12 surfaces, or I420 / YV12 planes with arbitrary
+ * strides, optionally bottom-up, which is what x264_frame_copy_picture takes (R/common/frame.c:185-216) -- for any subset of the batch
+ * in ONE launch, with x264_frame_expand_border_mod16 fused: every entry's element gets its whole coded area written (visible samples
+ * copied, columns / rows beyond them replicated); the outer padding and the elements not named keep their contents.  The source is
+ * never read beyond the visible width of a row or beyond the last visible row, and may have any alignment (aligned sources are read
+ * with wider loads).  A bottom-up surface is given with VFLIP and plane pointers at its FIRST stored row, or -- the reference's own
+ * form -- with pointers at the last stored row and negative pitches. */
+#define X264HIP_CSP_I420  0x0001   /* x264.h's values where it has them */
+#define X264HIP_CSP_YV12  0x0004
+#define X264HIP_CSP_NV12  0x0100   /* not in the reference: Y plane + interleaved UV plane */
+#define X264HIP_CSP_VFLIP 0x1000
+typedef struct {
+    int element;               /* batch element of `pic` this surface becomes */
+    int csp;                   /* one of the above | VFLIP */
+    const uint8_t *plane[3];   /* DEVICE pointers; NV12: plane[2] = NULL */
+    int pitch[3];              /* bytes, may be negative */
+} x264hip_surface;
+/* surfaces: host array of n entries (1..batch), any elements in any order, none twice.  staging_host (pinned, x264hip_host_alloc) and
+ * table_dev: n * x264hip_surface_bytes() each, left alone until the stream has passed the call.  Asynchronous on the context's stream:
+ * no synchronisation, no allocation; x264hip_frame_ctx_select's element is neither read nor changed.  Returns -1 with
+ * x264hip_last_error() and launches nothing for: n outside 1..batch, an element outside the batch or named twice, an unknown csp, a
+ * NULL plane the layout needs, |pitch| below the row's bytes (NV12's second plane: 2 * (width / 2)), NULL staging or table. */
+int    x264hip_picture_import(x264hip_frame_ctx *c, x264hip_picture *pic, const x264hip_surface *surfaces, int n,
+                              void *staging_host, void *table_dev);
+size_t x264hip_surface_bytes(void);
 /* synthetic source: batch element b becomes frame t0 + b * t_stride of the integer-only test clip (the generator of
  * x264_vs2008_amd/synth.py, bit for bit), padded to the coded size; asynchronous on the context's stream.  Benchmarks take their input
  * from here, so every (chain, frame) is a picture of its own and no upload is involved.  Returns -1 (nothing launched) when

@@ -38,6 +38,11 @@ class Picture(C.Structure):
                 ("lines_lowres", C.c_int)]
 
 
+class Surface(C.Structure):
+    """One device-resident source surface of x264hip_picture_import."""
+    _fields_ = [("element", C.c_int), ("csp", C.c_int), ("plane", C.c_void_p * 3), ("pitch", C.c_int * 3)]
+
+
 class CqmTables(C.Structure):
     _fields_ = [("quant4_mf", C.c_uint16 * (4 * 52 * 16)), ("quant4_bias", C.c_uint16 * (4 * 52 * 16)),
                 ("quant8_mf", C.c_uint16 * (2 * 52 * 64)), ("quant8_bias", C.c_uint16 * (2 * 52 * 64)),
@@ -210,7 +215,7 @@ class StatFrame(C.Structure):
 
 
 # C typedef name -> record; tables.py adds the seven of include/x264hip_tables.h
-RECORDS = {"x264hip_cfg": Cfg, "x264hip_frame_dims": Dims, "x264hip_picture": Picture, "x264hip_cqm_tables": CqmTables,
+RECORDS = {"x264hip_cfg": Cfg, "x264hip_frame_dims": Dims, "x264hip_picture": Picture, "x264hip_surface": Surface, "x264hip_cqm_tables": CqmTables,
            "x264hip_me_params": MeParams, "x264hip_me16_params": Me16Params, "x264hip_mb_state": MbState, "x264hip_slice_rd": SliceRd,
            "x264hip_slice_params": SliceParams, "x264hip_slice_b": SliceB, "x264hip_nr_state": NrState, "x264hip_residual_params": ResidualParams,
            "x264hip_deblock_params": DeblockParams, "x264hip_lookahead_params": LookaheadParams, "x264hip_look_need": Need,
@@ -271,6 +276,8 @@ PROTOTYPES = {
     "x264hip_frame_ctx_select": "i:pi",
     "x264hip_picture_upload": "i:pppipipi",
     "x264hip_picture_upload_async": "i:pppipipip",
+    "x264hip_picture_import": "i:pppipp",
+    "x264hip_surface_bytes": "z:",
     "x264hip_picture_synth": "i:ppii",
     "x264hip_picture_download": "i:ppipii",
     "x264hip_expand_border": "i:ppi",

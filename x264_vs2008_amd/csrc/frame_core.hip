@@ -71,6 +71,102 @@ __global__ __launch_bounds__(256) void k_synth_plane(u8 *pix, size_t bs, int str
     *(u32 *)(pix + bs * blockIdx.z + (size_t)yy * stride + xq) = out;
 }
 
+// x264_frame_copy_picture + x264_frame_expand_border_mod16 (R/common/frame.c:185-216, :303-334) for pictures that already lie in device
+// memory, every named batch element in one launch (x264hip_picture_import).  tab[blockIdx.z] is an x264hip_surface the host has put in
+// one form: planes in Y, U, V order (YV12's swap done), top-down (VFLIP folded into the pointer and a negated pitch), csp = I420 or NV12.
+// Access pattern: one lane makes 16 bytes of the coded area.  A luma lane loads 16 bytes of its source row and stores them as one
+// 16-byte vector; a chroma lane makes 8 bytes of U and 8 of V at the same position -- from two 8-byte loads (planar) or from one
+// 16-byte load of interleaved U,V split in registers with v_perm_b32 (NV12).  Both kinds have mb_w lanes per row; the blocks below
+// `luma_blocks` take the lines16 luma rows, the others the lines16 / 2 chroma rows, so a block is all of one kind.  Columns beyond the
+// visible width replicate the row's last sample, rows beyond the visible height read the last visible source row again: the source is
+// never read past the visible width of a row or past row h - 1, the destination never outside the coded area.
+// Alignment.  Destination: every plane's allocation is 256-byte aligned (hipMalloc; elements lie a multiple of 256 apart), its row
+// stride a multiple of 16, and pixel (0,0) lies padv * stride + padh into it with padh = 32 (luma) or 16 (chroma) -- so every row starts
+// on a 16-byte boundary in the luma AND in the chroma planes, a luma lane's 16-byte store at x = 16k is aligned and so is a chroma lane's
+// 8-byte store at x = 8k.  Source: pitches and bases are the decoder's.  Per entry and plane, (address | pitch) & 15 says what every row
+// of that plane allows: 0 in the low four bits -> vector loads of the lane's whole width, in the low three -> 8-byte loads, in the low
+// two -> dword loads, otherwise byte loads.  The choice depends on the entry alone, so it is uniform over a block; only the lane that holds the visible row's end leaves it.
+template <int N, int UNIT>       // N bytes from row[x0 ..), clamped to the last sample of the visible row (wv bytes, samples of UNIT bytes)
+__device__ __forceinline__ void import_load(const u8 *row_generic, int x0, int wv, int align, u32 (&out)[N / 4])
+{
+    // (a pointer read from the table is a generic one to the compiler: say that it is global memory, so the loads are global_load, not flat_load)
+#if defined(__HIP_DEVICE_COMPILE__)
+#define IMPORT_GLOBAL __attribute__((address_space(1)))
+#else
+#define IMPORT_GLOBAL
+#endif
+    typedef IMPORT_GLOBAL const u8 *gptr;
+    typedef IMPORT_GLOBAL const u32 *gptr32;
+    typedef IMPORT_GLOBAL const uint2 *gptr64;
+    typedef IMPORT_GLOBAL const uint4 *gptr128;
+#undef IMPORT_GLOBAL
+    const gptr row = (gptr)row_generic;
+    if (x0 + N <= wv && align >= 4) {
+        if (align >= N) {
+            if constexpr (N == 16) { const uint4 v = *(gptr128)(row + x0); out[0] = v.x; out[1] = v.y; out[2] = v.z; out[3] = v.w; }
+            else                   { const uint2 v = *(gptr64)(row + x0); out[0] = v.x; out[1] = v.y; }
+        } else if (align == 8) {               // (N == 16: a pitch such as width + 8)
+#pragma unroll
+            for (int i = 0; i < N / 8; i++) { const uint2 v = *(gptr64)(row + x0 + 8 * i); out[2 * i] = v.x; out[2 * i + 1] = v.y; }
+        } else {
+#pragma unroll
+            for (int i = 0; i < N / 4; i++) out[i] = *(gptr32)(row + x0 + 4 * i);
+        }
+        return;
+    }
+    // the lane that holds the row's visible end (or lies beyond it), and every lane of a plane without dword alignment: the dwords that
+    // lie wholly inside the row as dwords where the alignment allows, the rest byte by byte, clamped
+#pragma unroll
+    for (int i = 0; i < N / 4; i++) {
+        if (align >= 4 && x0 + 4 * i + 4 <= wv) { out[i] = *(gptr32)(row + x0 + 4 * i); continue; }
+        u32 v = 0;
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            const int x = x0 + 4 * i + k;                          // x0 is a multiple of UNIT, so x % UNIT == k % UNIT
+            v |= (u32)row[x < wv ? x : wv - UNIT + (k % UNIT)] << (8 * k);
+        }
+        out[i] = v;
+    }
+}
+__device__ __forceinline__ int import_align(const u8 *p, int pitch)
+{
+    const unsigned m = (unsigned)(uintptr_t)p | (unsigned)pitch;   // (the low bits of a negative pitch are those of its magnitude's negation: 0 together)
+    return (m & 15) == 0 ? 16 : (m & 7) == 0 ? 8 : (m & 3) == 0 ? 4 : 1;
+}
+__global__ __launch_bounds__(256) void k_import_planes(const x264hip_surface *__restrict__ tab, u8 *py, u8 *pu, u8 *pv, size_t bs_y, size_t bs_c,
+                                                       int stride_y, int stride_c, int w, int h, int mb_w, int lines16, int luma_blocks)
+{
+    const x264hip_surface s = tab[blockIdx.z];
+    const bool chroma = (int)blockIdx.x >= luma_blocks;
+    const int lane = ((int)blockIdx.x - (chroma ? luma_blocks : 0)) * 256 + (int)threadIdx.x;
+    const int yy = lane / mb_w, col = lane - yy * mb_w;
+    if (!chroma) {
+        if (yy >= lines16) return;
+        const u8 *row = s.plane[0] + (ptrdiff_t)(yy < h ? yy : h - 1) * s.pitch[0];
+        u32 v[4];
+        import_load<16, 1>(row, col * 16, w, import_align(s.plane[0], s.pitch[0]), v);
+        *(uint4 *)(py + bs_y * s.element + (size_t)yy * stride_y + col * 16) = make_uint4(v[0], v[1], v[2], v[3]);
+        return;
+    }
+    const int wc = w >> 1, hc = h >> 1;
+    if (yy >= lines16 / 2) return;
+    const int sy = yy < hc ? yy : hc - 1;
+    u32 a[2], b[2];
+    if (s.csp == X264HIP_CSP_NV12) {
+        u32 v[4];
+        import_load<16, 2>(s.plane[1] + (ptrdiff_t)sy * s.pitch[1], col * 16, 2 * wc, import_align(s.plane[1], s.pitch[1]), v);
+        // bytes U0 V0 U1 V1 | U2 V2 U3 V3 of two dwords -> U0 U1 U2 U3 and V0 V1 V2 V3 (selector bytes 0-3 take the second operand's, 4-7 the first's)
+        a[0] = __builtin_amdgcn_perm(v[1], v[0], 0x06040200u); b[0] = __builtin_amdgcn_perm(v[1], v[0], 0x07050301u);
+        a[1] = __builtin_amdgcn_perm(v[3], v[2], 0x06040200u); b[1] = __builtin_amdgcn_perm(v[3], v[2], 0x07050301u);
+    } else {
+        import_load<8, 1>(s.plane[1] + (ptrdiff_t)sy * s.pitch[1], col * 8, wc, import_align(s.plane[1], s.pitch[1]), a);
+        import_load<8, 1>(s.plane[2] + (ptrdiff_t)sy * s.pitch[2], col * 8, wc, import_align(s.plane[2], s.pitch[2]), b);
+    }
+    const size_t o = bs_c * s.element + (size_t)yy * stride_c + col * 8;
+    *(uint2 *)(pu + o) = make_uint2(a[0], a[1]);
+    *(uint2 *)(pv + o) = make_uint2(b[0], b[1]);
+}
+
 // plane_expand_border (R/common/frame.c:218-240) for the whole plane at once:
 // every padding byte takes the nearest interior pixel (left/right bands first,
 // then whole rows copied up/down, which is the same thing).
@@ -272,7 +368,8 @@ static void free_plane(u8 *p, int stride, int padh, int padv)
 extern "C" x264hip_frame_ctx *x264hip_frame_ctx_new(x264hip_frame_dims *d, void *hip_stream)
 {
     if (!initialised()) { set_error("x264hip_frame_ctx_new: call x264hip_init first"); return nullptr; }
-    if (d->width < 16 || d->height < 16 || d->width > 16384 || d->height > 16384) {
+    // (visible sizes below one macroblock are pictures like any other: the coded area is 16x16 and everything beyond the visible samples replicates)
+    if (d->width < 2 || d->height < 2 || d->width > 16384 || d->height > 16384) {
         set_error("unsupported frame size %dx%d", d->width, d->height);
         return nullptr;
     }
@@ -445,6 +542,48 @@ extern "C" int x264hip_picture_upload_async(x264hip_frame_ctx *c, x264hip_pictur
     HIPCHK(hipGetLastError());
     return 0;
 }
+
+// Device-resident surfaces -> batch elements of `pic`, all in one launch (k_import_planes).  The table convention is the chain table's
+// (x264hip_slice_sweep_chains): the host array is checked and rewritten into staging_host -- YV12's planes swapped (the reference's i^3),
+// VFLIP folded into a pointer at the last row and a negated pitch (x264_frame_copy_picture does the same), csp reduced to I420 or NV12 --
+// copied to table_dev on the context's stream, and the kernel reads it there.  No synchronisation, no allocation, the selected element
+// neither read nor changed.  Every refusal comes before the first enqueue.
+extern "C" int x264hip_picture_import(x264hip_frame_ctx *c, x264hip_picture *pic, const x264hip_surface *surfaces, int n, void *staging_host, void *table_dev)
+{
+    if (!c || !pic || !surfaces) { set_error("picture_import: context, picture or surfaces missing (x264hip_init and x264hip_frame_ctx_new come first)"); return -1; }
+    if (n < 1 || n > c->batch) { set_error("picture_import: %d surfaces for a batch of %d", n, c->batch); return -1; }
+    if (!staging_host || !table_dev) { set_error("picture_import: staging / table buffers missing"); return -1; }
+    const x264hip_frame_dims &d = c->d;
+    unsigned char named[4096 / 8] = {0};                               // (a batch has at most 4096 elements: x264hip_frame_ctx_new)
+    x264hip_surface *st = (x264hip_surface *)staging_host;
+    for (int i = 0; i < n; i++) {
+        x264hip_surface s = surfaces[i];
+        if (s.element < 0 || s.element >= c->batch) { set_error("picture_import: entry %d: element %d outside the batch of %d", i, s.element, c->batch); return -1; }
+        if (named[s.element >> 3] >> (s.element & 7) & 1) { set_error("picture_import: entry %d: element %d named twice", i, s.element); return -1; }
+        named[s.element >> 3] |= 1 << (s.element & 7);
+        const int layout = s.csp & ~X264HIP_CSP_VFLIP;
+        if (layout != X264HIP_CSP_I420 && layout != X264HIP_CSP_YV12 && layout != X264HIP_CSP_NV12) { set_error("picture_import: entry %d: unknown csp 0x%x", i, s.csp); return -1; }
+        const int n_planes = layout == X264HIP_CSP_NV12 ? 2 : 3;
+        if (layout == X264HIP_CSP_YV12) { const uint8_t *t = s.plane[1]; s.plane[1] = s.plane[2]; s.plane[2] = t; const int q = s.pitch[1]; s.pitch[1] = s.pitch[2]; s.pitch[2] = q; }
+        for (int k = 0; k < n_planes; k++) {
+            const int rows = d.height >> !!k;
+            const long long bytes = !k ? d.width : n_planes == 2 ? 2 * (d.width / 2) : d.width / 2, pitch = s.pitch[k];
+            if (!s.plane[k]) { set_error("picture_import: entry %d: plane %d is NULL", i, k); return -1; }
+            if ((pitch < 0 ? -pitch : pitch) < bytes) { set_error("picture_import: entry %d: plane %d: pitch %d is smaller than a row's %lld bytes", i, k, s.pitch[k], bytes); return -1; }
+            if (s.csp & X264HIP_CSP_VFLIP) { s.plane[k] += (ptrdiff_t)(rows - 1) * s.pitch[k]; s.pitch[k] = -s.pitch[k]; }
+        }
+        if (n_planes == 2) { s.plane[2] = nullptr; s.pitch[2] = 0; }
+        s.csp = n_planes == 2 ? X264HIP_CSP_NV12 : X264HIP_CSP_I420;
+        st[i] = s;
+    }
+    HIPCHK(hipMemcpyAsync(table_dev, st, sizeof(x264hip_surface) * (size_t)n, hipMemcpyHostToDevice, c->stream));
+    const int luma_blocks = (c->lines16 * d.mb_w + 255) / 256, chroma_blocks = (c->lines16 / 2 * d.mb_w + 255) / 256;
+    hipLaunchKernelGGL(k_import_planes, dim3(luma_blocks + chroma_blocks, 1, n), dim3(256), 0, c->stream, (const x264hip_surface *)table_dev,
+                       pic->plane[0], pic->plane[1], pic->plane[2], c->bs_y, c->bs_c, d.stride_y, d.stride_c, d.width, d.height, d.mb_w, c->lines16, luma_blocks);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+extern "C" size_t x264hip_surface_bytes(void) { return sizeof(x264hip_surface); }
 
 static int plane_geometry(const x264hip_frame_ctx *c, const x264hip_picture *pic, int id, u8 **p, int *stride, int *w, int *h, int *padh, int *padv)
 {

@@ -4,6 +4,7 @@
     python -m x264_vs2008_amd.encode --qp 26 --no-cabac --me dia --subme 0 --partitions none --no-deblock --scenecut -1 -o out.264 in.yuv 352x288
     python -m x264_vs2008_amd.encode --crf 23 --no-cabac --subme 5 --bframes 2 -o out.264 in.y4m      # CAVLC through the frame queue: CRF, B frames, scene cuts
     python -m x264_vs2008_amd.encode [options] -o out_%d.264 a.y4m b.y4m c.y4m        # one stream per input, coded side by side (same size and options)
+    python -m x264_vs2008_amd.encode --input-csp nv12 --qp 26 -o out.264 in_352x288.nv12                  # raw NV12 (Y plane, interleaved UV plane); also yv12, and --vflip
     python -m x264_vs2008_amd.encode --qp 0 -o out.264 in.y4m                         # lossless (High 4:4:4 Predictive SPS): what x264_validate_parameters
                                                                                       # turns off at QP 0 is off here too, the lookahead scores with SAD
 
@@ -18,7 +19,9 @@ product's throughput comes from thousands of streams in flight (bench.py); this 
 given at once are coded as chains of one batch.
 
 Readers: raw I420 (R/muxers.c:63-122: frame i at i * w * h * 3 / 2) and YUV4MPEG2 (:124-316: W, H, F from the stream header, C420* only, every
-FRAME header skipped to its newline).  Refused, never approximated: what the library refuses (x264hip_validate_parameters, the encoders' own
+FRAME header skipped to its newline).  Not the reference's: --input-csp yv12 / nv12 and --vflip say how a raw file's frames are laid out (x264_picture_t.img.i_csp
+has I420, YV12 and X264_CSP_VFLIP, its command line no option for them); such frames are not rearranged on the host -- every stream's frame is read into one
+pinned block, goes to the device in one copy and becomes the encoder's picture in one launch (x264hip_picture_import).  Refused, never approximated: what the library refuses (x264hip_validate_parameters, the encoders' own
 checks) -- ABR / VBV / 2-pass, --direct none, --no-cabac with --subme 6 and above (the RD levels), interlaced, threads > 1, b-pyramid.
 Every coded frame is measured as x264 does by default (PSNR, SSIM, macroblock statistics: --no-psnr / --no-ssim / --quiet turn that off, -v prints
 x264_encoder_frame_end's line per frame) and x264_encoder_close's report goes to stderr at the end, one per stream; the `.264` bytes do not depend on it.
@@ -35,10 +38,12 @@ import time
 import numpy as np
 
 from . import mux
+from .frame import CSP_I420, CSP_NV12, CSP_VFLIP, CSP_YV12
 
 ME = {"dia": 0, "hex": 1, "umh": 2, "esa": 3, "tesa": 4}
 DIRECT = {"none": 0, "spatial": 1, "temporal": 2, "auto": 3}
 CQM = {"flat": 0, "jvt": 1}
+INPUT_CSP = {"i420": CSP_I420, "yv12": CSP_YV12, "nv12": CSP_NV12}
 
 
 def build_parser():
@@ -97,6 +102,8 @@ def build_parser():
     a("--quiet", action="store_true", help="quiet mode: no statistics (a log level below INFO turns both measurements off, R/encoder/encoder.c:587-591)")
     a("-v", "--verbose", action="store_true", help="print stats for each frame")
     a("--device", type=int, default=0, help="GPU to run on")
+    a("--input-csp", default="i420", choices=sorted(INPUT_CSP), help="layout of raw input frames: i420 (Y, U, V), yv12 (Y, V, U), nv12 (Y, interleaved UV)")
+    a("--vflip", action="store_true", help="raw input frames are stored bottom-up")
     return ap
 
 
@@ -157,6 +164,12 @@ class RawYuv:
         w, h = self.w, self.h
         return b[:w * h].reshape(h, w), b[w * h:w * h * 5 // 4].reshape(h // 2, w // 2), b[w * h * 5 // 4:].reshape(h // 2, w // 2)
 
+    def read_into(self, i, out):
+        """Frame i as the file holds it, into the uint8 array `out` (self.size bytes)."""
+        self.f.seek(i * self.size)
+        if self.f.readinto(out) != self.size:
+            raise IOError("short read at frame %d" % i)
+
 
 class Y4m:
     def __init__(self, path):
@@ -195,6 +208,56 @@ class Y4m:
         b = np.frombuffer(self.f.read(self.size), np.uint8)
         w, h = self.w, self.h
         return b[:w * h].reshape(h, w), b[w * h:w * h * 5 // 4].reshape(h // 2, w // 2), b[w * h * 5 // 4:].reshape(h // 2, w // 2)
+
+
+class DeviceIngest:
+    """Input frames in a layout other than top-down I420: frame t of every source is read into ONE pinned block as the file holds it, copied
+    to ONE device buffer in one copy, and handed to the encoder as surfaces for one x264hip_picture_import -- the layout is undone by the
+    kernel, not on the host."""
+
+    def __init__(self, lib, sources, csp, vflip):
+        import ctypes as C
+        self.lib, self.sources, self.size = lib, sources, sources[0].size
+        w, h = sources[0].w, sources[0].h
+        if not all(hasattr(s, "read_into") for s in sources):
+            raise ValueError("--input-csp / --vflip go with raw input: a YUV4MPEG2 stream names its own layout")
+        if w % 2 or h % 2:
+            raise ValueError("--input-csp / --vflip: %dx%d: 4:2:0 surfaces have even sizes" % (w, h))
+        n = self.size * len(sources)
+        self.host = lib.x264hip_host_alloc(n)
+        self.dev = lib.x264hip_malloc(n)
+        self.ev = lib.x264hip_event_create()
+        if not self.host or not self.dev or not self.ev:
+            self.close()
+            raise MemoryError("--input-csp / --vflip: %d bytes of pinned and device memory" % n)
+        self.view = np.ctypeslib.as_array(C.cast(self.host, C.POINTER(C.c_uint8)), (len(sources), self.size))
+        self.busy = False
+        flags = csp | (CSP_VFLIP if vflip else 0)
+        if csp == INPUT_CSP["nv12"]:
+            self.layout = lambda base: (flags, (base, base + w * h, None), (w, w, 0))
+        else:                                      # the second and third plane as the file orders them: YV12 is the layout's name for V first
+            self.layout = lambda base: (flags, (base, base + w * h, base + w * h * 5 // 4), (w, w // 2, w // 2))
+
+    def surfaces(self, t, stream):
+        """Frame t of every source on the device, behind what `stream` holds: the entries for FrameCtx.import_surfaces on that stream."""
+        lib = self.lib
+        if self.busy and lib.x264hip_event_query(self.ev) != 1:        # the copy of the frame before still reads the pinned block
+            lib.x264hip_stream_synchronize(stream)
+        for b, s in enumerate(self.sources):
+            s.read_into(t, self.view[b])
+        if lib.x264hip_memcpy_h2d_async(self.dev, self.host, self.view.size, stream) != 0 or lib.x264hip_event_record(self.ev, stream) != 0:
+            raise RuntimeError("--input-csp / --vflip: frame %d to the device: %s" % (t, lib.x264hip_last_error().decode()))
+        self.busy = True
+        return [(b,) + self.layout(self.dev + b * self.size) for b in range(len(self.sources))]
+
+    def close(self):
+        if self.ev:
+            self.lib.x264hip_event_destroy(self.ev)
+        if self.dev:
+            self.lib.x264hip_free(self.dev)
+        if self.host:
+            self.lib.x264hip_host_free(self.host)
+        self.ev = self.dev = self.host = self.view = None
 
 
 def open_inputs(names):
@@ -236,7 +299,8 @@ def check_built(p):
                          "streams (--bframes 0); the B kernels do not keep the cache entries a macroblock leaves behind" % (p.subpel_refine, p.bframe))
 
 
-def encode_streams(lib, p, sources, n_frames, sinks, psnr=0, ssim=0, verbose=False, stats=None, observe=None, cabac_pass=None, cavlc_mp=None):
+def encode_streams(lib, p, sources, n_frames, sinks, psnr=0, ssim=0, verbose=False, stats=None, observe=None, cabac_pass=None, cavlc_mp=None,
+                   input_csp=INPUT_CSP["i420"], vflip=False):
     """p: validated parameters (mux.encoder_params); sources: readers of equal picture size; sinks: binary files, one per source.
     psnr / ssim: measure every coded frame (x264hip_frame_report_*); stats: a list that receives one quality.Stat per stream (the caller prints
     its summary and closes it); verbose: x264_encoder_frame_end's line per frame on stderr; observe(enc, chain, frame, slice type, picture, state,
@@ -246,8 +310,18 @@ def encode_streams(lib, p, sources, n_frames, sinks, psnr=0, ssim=0, verbose=Fal
     front of it is the macroblock-parallel one, measured faster; under --aq-mode 1 both choices code a frame on one wavefront
     per chain and nothing has been measured, so the in-loop writer stays; True / False force it either way.  The bytes are the same.
     cavlc_mp: who writes a --no-cabac slice wherever the CAVLC pass runs -- True: the macroblock-parallel pass (ChainEncoder(cavlc_mp=True):
-    count, scan, place), None / False: the serial pass; a ValueError where no CAVLC pass runs (CABAC).  The bytes are the same."""
+    count, scan, place), None / False: the serial pass; a ValueError where no CAVLC pass runs (CABAC).  The bytes are the same.
+    input_csp / vflip: the layout of the sources' frames (INPUT_CSP); anything but top-down I420 goes through DeviceIngest."""
     check_built(p)
+    ingest = DeviceIngest(lib, sources, input_csp, vflip) if input_csp != INPUT_CSP["i420"] or vflip else None
+    try:
+        return _encode_streams(lib, p, sources, n_frames, sinks, psnr, ssim, verbose, stats, observe, cabac_pass, cavlc_mp, ingest)
+    finally:
+        if ingest is not None:
+            ingest.close()
+
+
+def _encode_streams(lib, p, sources, n_frames, sinks, psnr, ssim, verbose, stats, observe, cabac_pass, cavlc_mp, ingest):
     from .quality import Stat
     if stats is not None:
         stats += [Stat(lib, p, psnr, ssim) for _ in sources]
@@ -290,8 +364,11 @@ def encode_streams(lib, p, sources, n_frames, sinks, psnr=0, ssim=0, verbose=Fal
         enc = sl.ChainEncoder(lib, w, h, cq, batch=B, write=1, cabac_pass=cabac_pass or None, mb_carry=carry, cavlc_mp=cavlc_mp, **common, **measure)
         try:
             for t in range(n_frames):
-                for b, s in enumerate(sources):
-                    enc.upload(*s.read(t), b=b)
+                if ingest is not None:
+                    enc.upload_device(ingest.surfaces(t, enc.ctx.stream))
+                else:
+                    for b, s in enumerate(sources):
+                        enc.upload(*s.read(t), b=b)
                 stype, qp, _ = enc.encode_frame()
                 enc.status()
                 pays = enc.payloads()
@@ -315,6 +392,9 @@ def encode_streams(lib, p, sources, n_frames, sinks, psnr=0, ssim=0, verbose=Fal
                         direct_pred=p.direct_mv_pred, cavlc_mp=cavlc_mp, **common, **measure)
 
     def fill(pic, f):
+        if ingest is not None:
+            enc.src_ctx.import_surfaces(pic, ingest.surfaces(f, enc.src_ctx.stream))
+            return
         for b, s in enumerate(sources):
             enc.src_ctx.upload(pic, *s.read(f), b=b)
 
@@ -340,6 +420,9 @@ def encode_streams(lib, p, sources, n_frames, sinks, psnr=0, ssim=0, verbose=Fal
 
 def main(argv=None):
     o = build_parser().parse_args(argv)
+    if (o.input_csp != "i420" or o.vflip) and any(n.lower().endswith(".y4m") for n in o.inputs):
+        raise SystemExit("encode: %s goes with raw input: a YUV4MPEG2 stream names its own layout (planar 4:2:0, U before V, top-down)"
+                         % ("--vflip" if o.input_csp == "i420" else "--input-csp " + o.input_csp))
     from . import lib as L
     sources = open_inputs(o.inputs)
     w, h = sources[0].w, sources[0].h
@@ -375,7 +458,8 @@ def main(argv=None):
     stats = None if rf["quiet"] else []
     t0 = time.time()
     try:
-        done = encode_streams(lib, p, sources, n, sinks, psnr=rf["psnr"], ssim=rf["ssim"], verbose=rf["verbose"], stats=stats, cavlc_mp=o.cavlc_mp or None)
+        done = encode_streams(lib, p, sources, n, sinks, psnr=rf["psnr"], ssim=rf["ssim"], verbose=rf["verbose"], stats=stats, cavlc_mp=o.cavlc_mp or None,
+                              input_csp=INPUT_CSP[o.input_csp], vflip=o.vflip)
     except (ValueError, RuntimeError) as ex:
         raise SystemExit("encode: " + str(ex))
     finally:

@@ -9,9 +9,10 @@ import ctypes as C
 
 import numpy as np
 
-from .abi import CqmTables, DeblockParams, Dims, Me16Params, MeParams, Picture, ResidualParams
+from .abi import CqmTables, DeblockParams, Dims, Me16Params, MeParams, Picture, ResidualParams, Surface
 
 PADH = PADV = 32
+CSP_I420, CSP_YV12, CSP_NV12, CSP_VFLIP = 0x0001, 0x0004, 0x0100, 0x1000      # X264HIP_CSP_* of include/x264hip.h
 
 
 class DeviceArray:
@@ -46,6 +47,8 @@ class DeviceArray:
             self.ptr = None
 
 
+IMPORT_SLOTS = 4          # FrameCtx.import_surfaces: tables in flight before a call has to wait
+
 PLANE_IDS = {"y": 0, "u": 1, "v": 2, "h": 3, "vv": 4, "c": 5, "l0": 6, "lh": 7, "lv": 8, "lc": 9}
 
 
@@ -61,6 +64,7 @@ class FrameCtx:
             raise RuntimeError("x264hip_frame_ctx_new failed: %s" % lib.x264hip_last_error().decode())
         self.h = C.c_void_p(self.h)
         self.pictures = []
+        self._import = None             # import_surfaces' pinned staging block and device table: made on first use
 
     @property
     def stream(self):
@@ -98,6 +102,45 @@ class FrameCtx:
         self.check(self.lib.x264hip_picture_upload(self.h, C.byref(pic), p(y), y.shape[1], p(u), u.shape[1],
                                                    p(v), v.shape[1]), "picture_upload")
 
+    def import_surfaces(self, pic, surfaces):
+        """Pictures that already lie in device memory become batch elements of `pic`, all in one launch and without a synchronisation
+        (x264hip_picture_import).  surfaces: [(element, csp, (ptr_y, ptr_u, ptr_v), (pitch_y, pitch_u, pitch_v))] -- csp one of CSP_I420,
+        CSP_YV12, CSP_NV12 (ptr_v None), optionally | CSP_VFLIP; device addresses, pitches in bytes and possibly negative; any subset of
+        the batch in any order.  Elements not named keep their contents.  The surfaces stay untouched until the context's stream has
+        passed the call.  The table convention asks the same of the staging block and the table, so the block is a ring of IMPORT_SLOTS
+        tables with an event each: calls may follow one another without a synchronisation in between, and only a call that finds its
+        slot's event still pending waits for the stream."""
+        lib = self.lib
+        if not surfaces:
+            raise ValueError("import_surfaces: no surfaces")
+        if self._import is None:
+            nbytes = lib.x264hip_surface_bytes() * self.batch
+            host = lib.x264hip_host_alloc(nbytes * IMPORT_SLOTS)
+            if not host:
+                raise MemoryError("x264hip_host_alloc(%d) failed" % (nbytes * IMPORT_SLOTS))
+            events = [lib.x264hip_event_create() for _ in range(IMPORT_SLOTS)]
+            if not all(events):
+                for ev in events:
+                    lib.x264hip_event_destroy(ev)
+                lib.x264hip_host_free(host)
+                raise MemoryError("x264hip_event_create failed")
+            self._import = dict(host=host, dev=DeviceArray(lib, (nbytes * IMPORT_SLOTS,), np.uint8), nbytes=nbytes, at=0,
+                                events=events, used=[False] * IMPORT_SLOTS)
+        im = self._import
+        slot = im["at"]                 # (taken for good only once the library has accepted the call)
+        if im["used"][slot] and lib.x264hip_event_query(im["events"][slot]) != 1:
+            self.sync()
+        entries = (Surface * len(surfaces))()
+        for e, (element, csp, planes, pitches) in zip(entries, surfaces):
+            e.element, e.csp = element, csp
+            for k in range(3):
+                e.plane[k] = planes[k] if k < len(planes) else None
+                e.pitch[k] = pitches[k] if k < len(pitches) and pitches[k] is not None else 0
+        self.check(lib.x264hip_picture_import(self.h, C.byref(pic), entries, len(surfaces), im["host"] + slot * im["nbytes"],
+                                              im["dev"].ptr + slot * im["nbytes"]), "picture_import")
+        self.check(lib.x264hip_event_record(im["events"][slot], self.stream), "event_record")
+        im["used"][slot], im["at"] = True, (slot + 1) % IMPORT_SLOTS
+
     def geometry(self, pic, name):
         d = self.dims
         i = PLANE_IDS[name]
@@ -125,6 +168,14 @@ class FrameCtx:
         for pic in self.pictures:
             self.lib.x264hip_picture_free(self.h, C.byref(pic))
         self.pictures = []
+        if self._import is not None:
+            if self.h:
+                self.lib.x264hip_sync(self.h)
+            self.lib.x264hip_host_free(self._import["host"])
+            self._import["dev"].free()
+            for ev in self._import["events"]:
+                self.lib.x264hip_event_destroy(ev)
+            self._import = None
         if self.h:
             self.lib.x264hip_frame_ctx_delete(self.h)
             self.h = None

@@ -201,6 +201,7 @@ class ChainEncoder:
             self.payload_cap = payload_cap or (n * MB_BYTES_AVG + MB_BYTES_MAX + 128 + PAYLOAD_LEAD)
             self.rd_bufs = self._frame_bufs(batch, n, self.payload_cap, 0)
         self.i_frame, self.i_frame_stride = 0, 0      # shard.py sets both when the chains are the GOPs of one stream
+        self.import_ev = None          # upload_device with lanes: the event the lanes' streams wait for
         self._fenc = None              # the picture upload() fills: allocated on first use (a caller with its own source pictures never needs it)
         # B frames (disposable, one list-1 picture): encode_frame(src, stype, disp) in coding_order(); the DPB then holds
         # max(n_refs, 2) pictures (sps->vui.i_max_dec_frame_buffering, R/encoder/set.c:196-200)
@@ -276,6 +277,24 @@ class ChainEncoder:
         for ln in self.lanes:          # a B frame still in flight on a lane may be reading this picture
             ln["ctx"].sync()
         self.ctx.upload(self.fenc, y, u, v, b=b)
+
+    def upload_device(self, surfaces):
+        """The same from pictures that already lie in device memory, any subset of the batch in one launch and without a synchronisation:
+        surfaces as FrameCtx.import_surfaces takes them, [(element, csp, (ptr_y, ptr_u, ptr_v), (pitch_y, pitch_u, pitch_v))].  Unlike
+        upload this returns before the picture is in place: what follows on the main stream is ordered behind it by the stream, and the
+        lanes' streams are made to wait for it here."""
+        L = self.lib
+        for ln in self.lanes:          # a B frame still in flight on a lane may be reading this picture
+            ln["ctx"].sync()
+        self.ctx.import_surfaces(self.fenc, surfaces)
+        if self.lanes:                 # a B frame coded next runs on a lane's own stream: behind the import, not beside it
+            if self.import_ev is None:
+                self.import_ev = L.x264hip_event_create()
+                if not self.import_ev:
+                    raise MemoryError("x264hip_event_create failed")
+            self.ctx.check(L.x264hip_event_record(self.import_ev, self.ctx.stream), "event_record")
+            for ln in self.lanes:
+                self.ctx.check(L.x264hip_stream_wait_event(ln["ctx"].stream, self.import_ev), "stream_wait_event")
 
     # ---- the records a sweep is given: built here for every encoder of this package --------------------------------------------------
     def ref_lists(self, refs, poc, stype):
@@ -487,7 +506,9 @@ class ChainEncoder:
             self.lib.x264hip_event_destroy(ev)
         if self.anchor_ev:
             self.lib.x264hip_event_destroy(self.anchor_ev)
-        self.b_readers, self.anchor_ev = [], None
+        if self.import_ev:
+            self.lib.x264hip_event_destroy(self.import_ev)
+        self.b_readers, self.anchor_ev, self.import_ev = [], None, None
         for r in self.reporters.values():
             r.close()
         self.reporters = {}

@@ -172,7 +172,14 @@ class StreamEncoder(ChainEncoder):
         return frames
 
     def step(self, fill):
-        """fill(picture, frame): write input picture `frame` of every chain into `picture` (enc.src_ctx.upload / .synth); None: flush.
+        """fill(picture, frame): write input picture `frame` of every chain into `picture` (enc.src_ctx.upload / .synth / .import_surfaces); None: flush.
+        Pictures that already lie in device memory (a decoder's NV12 surfaces) come in with one launch for all chains and no synchronisation;
+        a chain that has run out of input is simply not named and keeps its element:
+
+            def fill(picture, frame):
+                enc.src_ctx.import_surfaces(picture, [(b, CSP_NV12, (s.y_ptr, s.uv_ptr, None), (s.pitch, s.pitch, 0))
+                                                      for b, s in enumerate(decoded[frame]) if s is not None])
+
         Returns the list of Coded for the chains that coded a frame (empty while the B buffer fills; empty for good once flushed).
         With n_frames given to the constructor the next call's lookahead is prepared before this one returns (fill is then also asked
         for the following picture) and the flush starts by itself after n_frames pictures."""
@@ -502,6 +509,9 @@ class AsyncStreamEncoder(StreamEncoder):
         enc = AsyncStreamEncoder(lib, w, h, cqm, batch=B, n_frames=N, ...)
         enc.run(fill, on_launch)      # codes N frames of every chain; on_launch(coded, stream) after every launch (e.g. to enqueue a
                                       # payload copy behind it: a chain's payload buffer is reused by its next frame)
+
+    fill(picture, frame) is StreamEncoder.step's: enc.src_ctx.upload per chain, or enc.src_ctx.import_surfaces(picture, surfaces) once for the chains
+    whose pictures already lie in device memory (frame.CSP_I420 / CSP_YV12 / CSP_NV12, optionally | CSP_VFLIP) -- asynchronous on the lookahead's stream.
     """
 
     def __init__(self, lib, width, height, cqm, batch=1, n_frames=None, drift=2, launches=8, **kw):
